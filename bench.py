@@ -8,7 +8,13 @@ inputs are resident in HBM; its host cost is reported separately (``jpeg_host_ms
 Metric: Mpixels/s = B*H*W*world / step time (whole job).  Multi-GPU: one process per GPU, batches
 shard over ranks (weak scaling), gradients all-reduced over RCCL (hyres_hip.ddp).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline figure only).
+``--dump-outputs DIR`` also writes what the last timed step returned (and the parameters it left) as
+``DIR/<name>.npy``; the inputs, weights and noise seeds are fixed, so two builds can be compared array for array.
+``--full`` adds every other leg to the line: the per-kernel roofline, the fp32-GEMM and branch-stream A/Bs, the eval /
+Kodak / codec legs, the f16-amp leg, the host-JPEG legs and the CPU baseline (each with its own ``--no-*`` switch).
 """
 from __future__ import annotations
 
@@ -53,7 +59,48 @@ def parse():
     ap.add_argument("--jpeg-procs", type=int, default=None, help="JPEG worker processes (default min(8, cpus))")
     ap.add_argument("--fp32-gemm", choices=["default", "native", "bf16x6"], default="default",
                     help="fp32 conv GEMMs: the native fp32 MFMA or the bf16x6 split (hyres_conv_tuning key 7)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (and the parameters after it) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, A/B, eval, codec, f16-amp, host-JPEG and CPU-baseline legs")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6  # all of --dump-outputs together
+DUMP_SAMPLE_SEED = 1926
+
+
+def step_outputs(out, c, flat_params):
+    """What a caller of the timed step receives, as host arrays: the forward's outputs, the loss terms and the
+    parameters the optimiser left. Copied off the device at once (a replay's outputs live in the graph's pool)."""
+    arrays = {"x_hat": out["x_hat"], "y_likelihoods": out["likelihoods"]["y"],
+              "z_likelihoods": out["likelihoods"]["z"], "params": flat_params}
+    for k, v in c.items():
+        if isinstance(v, torch.Tensor):
+            arrays["loss" if k == "loss" else f"loss_{k}"] = v
+    res = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        res[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    return res
+
+
+def dump_outputs(path, arrays):
+    """``path/<name>.npy`` per array, float32 / float64, at most DUMP_BUDGET_BYTES in all (headers included): the
+    arrays are written smallest first, each whole while it fits an equal share of what is left of the budget, else
+    as a fixed (seeded, sorted) sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 4096 * len(arrays)  # room for the .npy headers
+    order = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    for i, name in enumerate(order):
+        a = np.ascontiguousarray(arrays[name])
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            idx = np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(args, budget_s):
@@ -563,15 +610,74 @@ def analysis_synthesis(net, x, reps):
     return res
 
 
+def fp32_gemm_mode(L):
+    """The fp32 convs' GEMM (hyres_conv_tuning key 7: 1 bf16x6, 0 the native fp32 MFMA)."""
+    cur = ctypes.c_int(0)
+    L.call("hyres_conv_tuning", 7, 1, ctypes.byref(cur))  # read (and restore) the current mode
+    L.call("hyres_conv_tuning", 7, cur.value, None)
+    return "bf16x6" if cur.value == 1 else "native"
+
+
+def result_line(args, world, elapsed, loss_val, jpeg_ms, graph, dist_mode, fp32_gemm, legs=None):
+    """The result line: the headline (``elapsed`` seconds for the ``args.steps`` timed steps of the whole job) and,
+    from a --full run, the other legs (``legs``; None in a plain run)."""
+    legs = legs or {}
+    B, S = args.batch, args.size
+    line = {
+        "metric": "Mpixels/s encode+decode (N=128,M=192,256\u00d7256) at 1/2/4/8 GPU; bpp+PSNR parity",
+        "metric_definition": ("BASELINE.json's metric, measured on configs[1] (the workload it is quoted on): one "
+                              "step = forward (g_a 'encode' + hyperprior + checkerboard context + g_s 'decode' + "
+                              "MultiScaleRefine) + RD-loss backward + clip + Adam + aux Adam at bs=16 per GPU, "
+                              "device-only (host JPEG precomputed). This TRAIN-STEP rate is stricter than "
+                              "SURVEY §8d's 'encode+decode' = eval-forward rate, which is reported as "
+                              "'encode_decode_eval' (eval.bs16_256x256; C3's bs=32 in eval.bs32_256x256); the "
+                              "with-host-JPEG rates are in 'host_jpeg'"),
+        "encode_decode_eval": None if not legs.get("eval") else {
+            k: v["mpix_s"] for k, v in legs["eval"].items() if k.startswith("bs") and "mpix_s" in v},
+        "value": round(world * B * S * S * args.steps / elapsed / 1e6, 4),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1000 / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic uniform 8-bit RGB, recipe-initialised weights (no checkpoint ships)",
+        "config": {"workload": "C2 train step (configs[1]): ResidualJPEGCompression N=128 M=192, fwd+bwd+"
+                               "optimizer, lambda=0.045, noisequant=False, JPEG q50 precomputed on host",
+                   "global_batch": B * world, "image": [S, S], "parallelism": f"dp{world}"},
+        "fp32_gemm": fp32_gemm,
+        "fp32_gemm_note": FP32_GEMM_NOTE[fp32_gemm],
+        "fp32_gemm_ab": legs.get("fp32_gemm_ab"),
+        "branch_streams_off_ab": legs.get("branch_streams_off_ab"),
+        "roofline": legs.get("roofline"),
+        "graph": graph,
+        "dist_mode": dist_mode,
+        "eval": legs.get("eval"),
+        "cpu_baseline": legs.get("cpu_baseline"),
+        "jpeg_host_ms_per_image": round(jpeg_ms, 3),
+        "host_jpeg": legs.get("host_jpeg"),
+        "amp": legs.get("amp"),
+        "loss": loss_val,
+        "full": bool(args.full),
+    }
+    return line
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # host JPEG worker processes: spawned before this process touches the GPU (hyres_hip.jpeg_host); only
-    # the N = 1 run times the host JPEG legs, so N > 1 ranks code their one setup batch in-process (no
-    # 8 workers per rank on a full node)
+    # the N = 1 --full run times the host JPEG legs, so a plain run and N > 1 ranks code their one setup batch
+    # in-process (no 8 workers per rank on a full node)
     from hyres_hip import jpeg_host
-    jpeg_host.start(args.jpeg_procs if world == 1 else 0)
+    jpeg_host.start(args.jpeg_procs if world == 1 and args.full and not args.no_host_jpeg else 0)
     rank = int(os.environ.get("RANK", "0"))
+    # the training-noise seeds (hyres_hip.entropy_ops.NoiseSource) are drawn from torch's CPU generator: fixed, so
+    # that the same arguments give the same step from run to run (--dump-outputs)
+    torch.manual_seed(1926 + rank)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dist = world > 1 or os.environ.get("HYRES_BENCH_FORCE_DIST") == "1"  # rehearse the RCCL path at N=1
     # rehearsal knobs for the N>1 path on a one-GPU box: HYRES_BENCH_ONE_GPU=1 puts every rank on device 0,
@@ -646,14 +752,14 @@ def main():
         gr = gr or graphed
         if gr is not None and not eager:
             between = reducer.launch_segments if (reducer is not None and gr.split_at) else None
-            return gr.replay(between=between)[1]
+            return gr.replay(between=between)
         out = net.forward_device(x, jpeg, jpeg_bpp, noisequant=False)
         c = crit(out, x)
         c["loss"].backward()
-        return c
+        return out, c
 
-    def step(eager=False, gr=None):
-        c = fwd_bwd(eager, gr)
+    def step(eager=False, gr=None, with_out=False):
+        out, c = fwd_bwd(eager, gr)
         if reducer is not None:
             reducer.all_reduce()
         opt.step()
@@ -662,7 +768,7 @@ def main():
         aux.backward()
         aux_opt.step()
         aux_opt.zero_grad()
-        return c
+        return (out, c) if with_out else c
 
     def step_eager_cpu(xc, x_next):
         """train.sh's path: model(d) on a CPU batch (host JPEG inline), eager, + loss/backward/optimiser."""
@@ -699,14 +805,32 @@ def main():
     torch.cuda.synchronize()
     t0 = time.time()
     for i in range(args.steps):
-        c = step()
+        out, c = step(with_out=True)
     torch.cuda.synchronize()
     if dist:
         tdist.barrier()
     torch.cuda.synchronize()
     elapsed = time.time() - t0
     loss_val = float(c["loss"].detach())
-    c = None  # replay outputs live in the graph's pool: none may be held when the graph is closed
+    if args.dump_outputs and rank == 0:
+        # the parameters themselves, in name order (the flat buffer's alignment padding is uninitialised)
+        dump_outputs(args.dump_outputs, step_outputs(
+            out, c, torch.cat([p.detach().reshape(-1) for p in main_p + aux_p])))
+    out = c = None  # replay outputs live in the graph's pool: none may be held when the graph is closed
+    if not args.full:
+        # a plain run: the headline figure only (every other leg, the roofline included, is behind --full)
+        if dist:
+            t = torch.tensor([elapsed], device=dev)
+            tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
+            elapsed = float(t)
+        if graphed is not None:
+            graphed.close()
+        if rank == 0:
+            print(json.dumps(result_line(args, world, elapsed, loss_val, jpeg_ms, graphed is not None, dist_mode,
+                                         fp32_gemm_mode(L))))
+        if dist:
+            tdist.destroy_process_group()
+        return
     # dominant-kernel roofline, measured live with HIP events (on the stream each conv launch goes to:
     # torch's current stream, also inside the branch streams) around every conv_fwd_kernel launch of one
     # eager step of the same workload right after the timed region (a graph replay cannot carry
@@ -736,8 +860,6 @@ def main():
         t = torch.tensor([elapsed], device=dev)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = float(t)
-    ms = elapsed * 1000 / args.steps
-    value = world * B * S * S * args.steps / elapsed / 1e6
 
     achieved = ks["flops"] / (ks["total_ms"] * 1e-3) / 1e12 if ks["total_ms"] > 0 else 0.0
     # the same instantiation's entry in the isolated steps (it need not be the top kernel there)
@@ -756,10 +878,8 @@ def main():
         return
     # the fp32 convs' GEMM (hyres_conv_tuning key 7: 1 bf16x6, 0 the native fp32 MFMA); the same step is re-captured
     # and timed once more on the other GEMM (A/B on this box)
-    cur = ctypes.c_int(0)
-    L.call("hyres_conv_tuning", 7, 1, ctypes.byref(cur))  # read (and restore) the current mode
-    L.call("hyres_conv_tuning", 7, cur.value, None)
-    fp32_gemm = "bf16x6" if cur.value == 1 else "native"
+    fp32_gemm = fp32_gemm_mode(L)
+    cur = ctypes.c_int(1 if fp32_gemm == "bf16x6" else 0)
     other = None
     if world == 1 and graphed is not None:
         from hyres_hip.graphs import CapturedStep
@@ -818,59 +938,24 @@ def main():
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, args.cpu_baseline_seconds)
-    line = {
-        "metric": "Mpixels/s encode+decode (N=128,M=192,256\u00d7256) at 1/2/4/8 GPU; bpp+PSNR parity",
-        "metric_definition": ("BASELINE.json's metric, measured on configs[1] (the workload it is quoted on): one "
-                              "step = forward (g_a 'encode' + hyperprior + checkerboard context + g_s 'decode' + "
-                              "MultiScaleRefine) + RD-loss backward + clip + Adam + aux Adam at bs=16 per GPU, "
-                              "device-only (host JPEG precomputed). This TRAIN-STEP rate is stricter than "
-                              "SURVEY §8d's 'encode+decode' = eval-forward rate, which is reported as "
-                              "'encode_decode_eval' (eval.bs16_256x256; C3's bs=32 in eval.bs32_256x256); the "
-                              "with-host-JPEG rates are in 'host_jpeg'"),
-        "encode_decode_eval": None if not evals else {
-            k: evals[k]["mpix_s"] for k in evals if k.startswith("bs") and "mpix_s" in evals[k]},
-        "value": round(value, 4),
-        "unit": "Mpixels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic uniform 8-bit RGB, recipe-initialised weights (no checkpoint ships)",
-        "config": {"workload": "C2 train step (configs[1]): ResidualJPEGCompression N=128 M=192, fwd+bwd+"
-                               "optimizer, lambda=0.045, noisequant=False, JPEG q50 precomputed on host",
-                   "global_batch": B * world, "image": [S, S], "parallelism": f"dp{world}"},
-        "fp32_gemm": fp32_gemm,
-        "fp32_gemm_note": FP32_GEMM_NOTE[fp32_gemm],
-        "fp32_gemm_ab": other,
-        "branch_streams_off_ab": serial,
-        "roofline": {"bound": "mfma", "kernel": f"{ks['kernel']} ({kernel_label(ks['kernel'])})",
-                     "achieved": round(achieved, 3), "peak": kernel_peak(ks["kernel"]), "unit": "TFLOP/s",
-                     "peak_note": peak_note(ks["kernel"]),
-                     "frac": round(achieved / kernel_peak(ks["kernel"]), 4),
-                     "frac_vs_native_fp32_peak": round(achieved / MI355X_FP32_PEAK_TFLOPS, 4),
-                     "traffic": traffic_bytes_per_launch(ks["kernel"]),
-                     "launches_per_step": ks["launches"], "avg_launch_us": round(ks["avg_us"], 2),
-                     "flops_per_launch": ks["flops_per_launch"],
-                     "algorithmic_bytes_per_launch": ks["bytes_per_launch"],
-                     "timing": f"HIP events around each launch of {EAGER_TIMED} eager steps after the timed region",
-                     "achieved_isolated": None if iso is None else round(iso, 3),
-                     "frac_isolated": None if iso is None else round(iso / kernel_peak(ks["kernel"]), 4),
-                     "avg_launch_us_isolated": None if iso_us is None else round(iso_us, 2),
-                     "ms_by_variant": ks.get("by_variant_ms"),
-                     "families": ks.get("families")},
-        "graph": graphed is not None,
-        "dist_mode": dist_mode,
-        "eval": evals,
-        "cpu_baseline": cpu,
-        "jpeg_host_ms_per_image": round(jpeg_ms, 3),
-        "host_jpeg": host,
-        "amp": amp,
-        "loss": loss_val,
-    }
+    roofline = {"bound": "mfma", "kernel": f"{ks['kernel']} ({kernel_label(ks['kernel'])})",
+                "achieved": round(achieved, 3), "peak": kernel_peak(ks["kernel"]), "unit": "TFLOP/s",
+                "peak_note": peak_note(ks["kernel"]),
+                "frac": round(achieved / kernel_peak(ks["kernel"]), 4),
+                "frac_vs_native_fp32_peak": round(achieved / MI355X_FP32_PEAK_TFLOPS, 4),
+                "traffic": traffic_bytes_per_launch(ks["kernel"]),
+                "launches_per_step": ks["launches"], "avg_launch_us": round(ks["avg_us"], 2),
+                "flops_per_launch": ks["flops_per_launch"],
+                "algorithmic_bytes_per_launch": ks["bytes_per_launch"],
+                "timing": f"HIP events around each launch of {EAGER_TIMED} eager steps after the timed region",
+                "achieved_isolated": None if iso is None else round(iso, 3),
+                "frac_isolated": None if iso is None else round(iso / kernel_peak(ks["kernel"]), 4),
+                "avg_launch_us_isolated": None if iso_us is None else round(iso_us, 2),
+                "ms_by_variant": ks.get("by_variant_ms"),
+                "families": ks.get("families")}
+    line = result_line(args, world, elapsed, loss_val, jpeg_ms, graphed is not None, dist_mode, fp32_gemm,
+                       {"eval": evals, "fp32_gemm_ab": other, "branch_streams_off_ab": serial, "roofline": roofline,
+                        "cpu_baseline": cpu, "host_jpeg": host, "amp": amp})
     print(json.dumps(line))
     if dist:
         tdist.destroy_process_group()

@@ -16,7 +16,7 @@ for rep in 1 2; do
       timeout -k 10 120 python3 scripts/conv_micro.py --H $H --bf6 --res --relu > gpurun_out/ab_micro.log 2>&1 || exit 1
       echo "$v rep$rep $(grep 'us,' gpurun_out/ab_micro.log)" >> $out
     done
-    timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-eval --no-amp --no-host-jpeg --no-cpu-baseline \
+    timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-eval --no-amp --no-host-jpeg --no-cpu-baseline \
       > gpurun_out/ab_bench.log 2>&1 || exit 1
     echo "$v rep$rep $(grep '^{' gpurun_out/ab_bench.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("step", d["ms_per_step"], "ms;", d["roofline"]["kernel"][:28], d["roofline"]["avg_launch_us"], "us live,", d["roofline"]["avg_launch_us_isolated"], "us isolated")')" >> $out
   done

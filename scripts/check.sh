@@ -15,14 +15,14 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 tag=$1; shift
-BENCH="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-eval"
+BENCH="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-eval"
 for ph in "$@"; do
   case $ph in
     tests) scripts/gpu_run.sh "gputests:600:python -u -m pytest tests -x -v --timeout 120 --timeout-method thread -m gpu -s" || exit $? ;;
     tests1) scripts/gpu_run.sh "gputests:600:python -u -m pytest tests -x -v --timeout 120 --timeout-method thread -m gpu -s --deselect tests/test_parity_gpu.py::test_amp_matches_reference_autocast_fixture" || exit $? ;;
     ampfix) scripts/gpu_run.sh "ampfix:200:python -u -m pytest tests/test_parity_gpu.py -v --timeout 180 --timeout-method thread -m gpu -s -k test_amp_matches_reference_autocast_fixture" ;;
     smoke) scripts/gpu_run.sh "smoke:200:python -c 'import __graft_entry__ as g; g.smoke()'" || exit $? ;;
-    bench) scripts/gpu_run.sh "bench_full:500:python3 bench.py --gpus 1 --steps 20 --warmup 5" || exit $?
+    bench) scripts/gpu_run.sh "bench_full:500:python3 bench.py --full --gpus 1 --steps 20 --warmup 5" || exit $?
            grep '^{' gpurun_out/bench_full.log > gpurun_out/${tag}_bench_line.json ;;
     stats) scripts/gpu_run.sh "stats:400:rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_stats -o run -- python3 $BENCH" || exit $?
            python3 scripts/prof_summary.py gpurun_out/${tag}_stats/run_kernel_stats.csv 11 > gpurun_out/${tag}_bench_summary.txt ;;

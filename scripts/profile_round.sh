@@ -5,9 +5,9 @@ set -o pipefail
 tag=${1:-r1}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
-BENCH="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-eval"
+BENCH="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-eval"
 scripts/gpu_run.sh \
-  "bench_full:420:python3 bench.py" \
+  "bench_full:420:python3 bench.py --full" \
   "stats:400:rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_stats -o run -- python3 $BENCH" \
   "pmc_fetch:500:rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/${tag}_pmc_fetch -o run -- python3 $BENCH" \
   "pmc_write:500:rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/${tag}_pmc_write -o run -- python3 $BENCH"

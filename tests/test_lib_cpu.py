@@ -266,3 +266,27 @@ def test_bench_prices_each_kernel_with_its_own_pmc_summary():
         assert got == want and got > 0
     assert b.traffic_bytes_per_launch("no_such_kernel") is None
     assert b.traffic_bytes_per_launch(None) is None
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float .npy per array, small arrays whole, an array above its share of the byte
+    budget as the same seeded sample of its elements on every call, the files together within the budget."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 64 * 1024)
+    rng = np.random.default_rng(0)
+    arrays = {"small": rng.random((3, 5)).astype(np.float32), "loss": np.float64(1.5) * np.ones(()),
+              "big": rng.random(50000).astype(np.float32), "bigger": rng.random((300, 300))}
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{n}.npy" for n in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 1024
+    assert np.array_equal(got["small"], arrays["small"]) and got["loss"] == 1.5
+    for n in ("big", "bigger"):
+        assert got[n].dtype == arrays[n].dtype and got[n].ndim == 1 and 0 < got[n].size < arrays[n].size
+        assert np.isin(got[n], arrays[n]).all()
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
