@@ -1,0 +1,426 @@
+// Device JPEG 4:2:2 base layer: encode -> decode round trip of a [B,3,H,W] fp32 batch on the
+// stream, bit-exact with libjpeg-turbo (the arithmetic lives in jpeg_core.h, shared with the host round trip).
+//
+//   jpeg_blocks_kernel    one thread per 8x8 block: pixels -> bytes -> Y / downsampled Cb / Cr -> forward DCT ->
+//                         quantise -> int16 zigzag coefficients [B][blocks][64] (scan order), and in the same pass
+//                         dequantise -> inverse DCT -> u8 Y / Cb / Cr planes
+//   jpeg_decode_kernel    fancy h2v1 upsample + YCbCr -> BGR + /255 into the fp32 NCHW output
+//   jpeg_count_kernel     Huffman bit count per block (DC predicted from the previous block of the component)
+//   jpeg_scan_kernel      exclusive scan of the bit counts per image -> every block's bit offset
+//   jpeg_pack_kernel      each block's code words at its offset into a big-endian word buffer that
+//                         jpeg_clear_kernel zeroed (atomicOr on the two words a block shares with its neighbours,
+//                         plain stores between them)
+//   jpeg_ff_count/scan/emit   count 0xFF bytes per 1 KiB chunk, scan, and write header + stuffed bytes + EOI and the
+//                         per-image byte count
+// No kernel syncs the host, allocates or copies to the host; every grid depends on the shape alone, so the round
+// trip can be captured into a graph.
+#include "common.h"
+#include "jpeg_core.h"
+
+#include <cstring>
+#include <utility>
+#include <vector>
+
+namespace hyres {
+namespace jpeg {
+
+__constant__ HuffTables d_huff = make_huff_tables();
+
+struct HeaderArg {
+    uint8_t b[kHeaderBytes + 1];
+};
+
+constexpr int kThreads = 256;
+constexpr int kChunkWords = kThreads;  // one stream word per thread: 1 KiB chunks
+
+struct Layout {
+    int nb, nwords, nchunks;
+    long long coef, yp, cbp, crp, bits, total, words, ff, end;
+};
+
+static long long align256(long long v) { return (v + 255) & ~255LL; }
+
+static Layout make_layout(int B, int H, int W) {
+    Layout L;
+    L.nb = blocks_per_image(H, W);
+    const long long w = ((long long)L.nb * kMaxBlockBits) / 32 + 1;
+    L.nchunks = (int)((w + kChunkWords - 1) / kChunkWords);
+    L.nwords = L.nchunks * kChunkWords;
+    long long o = 0;
+    L.coef = o, o = align256(o + (long long)B * L.nb * 64 * 2);
+    L.yp = o, o = align256(o + (long long)B * H * W);
+    L.cbp = o, o = align256(o + (long long)B * H * (W / 2));
+    L.crp = o, o = align256(o + (long long)B * H * (W / 2));
+    L.bits = o, o = align256(o + (long long)B * L.nb * 4);
+    L.total = o, o = align256(o + (long long)B * 4);
+    L.words = o, o = align256(o + (long long)B * L.nwords * 4);
+    L.ff = o, o = align256(o + (long long)B * L.nchunks * 4);
+    L.end = o;
+    return L;
+}
+
+// exclusive scan of one value per thread over a 256-thread block; total = the block's sum
+__device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < kThreads; off <<= 1) {
+        const int t = tid >= off ? sh[tid - off] : 0;
+        __syncthreads();
+        sh[tid] += t;
+        __syncthreads();
+    }
+    const int incl = sh[tid];
+    total = sh[kThreads - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+template <size_t... K>
+__device__ __forceinline__ void store_zigzag(int16_t* o, const int* d, std::index_sequence<K...>) {
+    // 32 packed pairs of zigzag-ordered coefficients, eight 16-byte stores
+    const uint32_t w[32] = {((uint32_t)(uint16_t)d[kNatural[2 * K]] | ((uint32_t)(uint16_t)d[kNatural[2 * K + 1]] << 16))...};
+#pragma unroll
+    for (int g = 0; g < 8; ++g)
+        reinterpret_cast<uint4*>(o)[g] = make_uint4(w[4 * g], w[4 * g + 1], w[4 * g + 2], w[4 * g + 3]);
+}
+
+// item i of an image: luminance blocks in raster order first (coalesced loads), then Cb, then Cr
+__global__ __launch_bounds__(kThreads) void jpeg_blocks_kernel(const float* __restrict__ x, int B, int H, int W,
+                                                              QuantTables Q, int16_t* __restrict__ coef,
+                                                              uint8_t* __restrict__ yp, uint8_t* __restrict__ cbp,
+                                                              uint8_t* __restrict__ crp) {
+    __shared__ uint16_t q[128];
+    if (threadIdx.x < 128) q[threadIdx.x] = Q.q[threadIdx.x >> 6][threadIdx.x & 63];
+    __syncthreads();
+    const int mw = W / 16, nmcu = mw * (H / 8), nb = 4 * nmcu;
+    const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (gid >= (long long)B * nb) return;
+    const int b = (int)(gid / nb), i = (int)(gid % nb);
+    int comp, bx, by, blk;
+    if (i < 2 * nmcu) {
+        comp = 0, bx = i % (2 * mw), by = i / (2 * mw);
+        blk = (by * mw + (bx >> 1)) * 4 + (bx & 1);
+    } else {
+        comp = i < 3 * nmcu ? 1 : 2;
+        const int m = i - (comp + 1) * nmcu;
+        bx = m % mw, by = m / mw;
+        blk = m * 4 + comp + 1;
+    }
+    const uint16_t* qt = q + (comp ? 64 : 0);
+    int d[64];
+    sample_block(x + (long long)b * 3 * H * W, H, W, comp, bx, by, d);
+    fdct_islow(d);
+    quantize(d, qt);
+    store_zigzag(coef + ((long long)b * nb + blk) * 64, d, std::make_index_sequence<32>());
+    dequant_idct(d, qt);
+    const int pw = comp ? W / 2 : W;
+    uint8_t* plane = (comp == 0 ? yp : (comp == 1 ? cbp : crp)) + (long long)b * H * pw;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        uint32_t u[8];  // samples in 0..255
+#pragma unroll
+        for (int c = 0; c < 8; ++c) u[c] = (uint32_t)d[r * 8 + c];
+        const uint32_t lo = u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24);
+        const uint32_t hi = u[4] | (u[5] << 8) | (u[6] << 16) | (u[7] << 24);
+        *reinterpret_cast<uint2*>(plane + (long long)(by * 8 + r) * pw + bx * 8) = make_uint2(lo, hi);
+    }
+}
+
+// one thread per chroma sample: output columns 2i and 2i+1 of the three planes (plane 0 = B)
+__global__ __launch_bounds__(kThreads) void jpeg_decode_kernel(const uint8_t* __restrict__ yp,
+                                                              const uint8_t* __restrict__ cbp,
+                                                              const uint8_t* __restrict__ crp, int B, int H, int W,
+                                                              float* __restrict__ out) {
+    const int cw = W / 2;
+    const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (gid >= (long long)B * H * cw) return;
+    const int i = (int)(gid % cw);
+    const long long row = gid / cw;  // b * H + r
+    const int b = (int)(row / H), r = (int)(row % H);
+    int cb[2], cr[2];
+    upsample_pair(cbp + row * cw, cw, i, cb[0], cb[1]);
+    upsample_pair(crp + row * cw, cw, i, cr[0], cr[1]);
+    float v[3][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        int R, G, Bl;
+        ycc_to_rgb(yp[row * W + 2 * i + h], cb[h], cr[h], R, G, Bl);
+        v[0][h] = __fdiv_rn((float)Bl, 255.0f);  // a true fp32 division, not a reciprocal multiply
+        v[1][h] = __fdiv_rn((float)G, 255.0f);
+        v[2][h] = __fdiv_rn((float)R, 255.0f);
+    }
+    const long long plane = (long long)H * W;
+    float* o = out + (long long)b * 3 * plane + (long long)r * W + 2 * i;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<float2*>(o + c * plane) = make_float2(v[c][0], v[c][1]);
+}
+
+__device__ __forceinline__ int pred_dc(const int16_t* coef_img, int blk) {
+    const int pb = dc_predecessor(blk);
+    return pb < 0 ? 0 : (int)coef_img[(long long)pb * 64];
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_count_kernel(const int16_t* __restrict__ coef, int B, int nb,
+                                                             int* __restrict__ bits) {
+    const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (gid >= (long long)B * nb) return;
+    const int blk = (int)(gid % nb);
+    const int16_t* img = coef + (gid - blk) * 64;
+    CountSink s;
+    encode_block(img + (long long)blk * 64, pred_dc(img, blk), d_huff, (blk & 3) < 2 ? 0 : 1, s);
+    bits[gid] = s.bits;
+}
+
+// one work-group per image: bits[] -> exclusive bit offsets in place, total[b] = the image's bit count
+__global__ __launch_bounds__(kThreads) void jpeg_scan_kernel(int* __restrict__ v, int n, int* __restrict__ total) {
+    __shared__ int sh[kThreads];
+    int* p = v + (long long)blockIdx.x * n;
+    int carry = 0;
+    for (int base = 0; base < n; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const int x = i < n ? p[i] : 0;
+        int sum;
+        const int e = block_excl_scan(x, sh, sum);
+        if (i < n) p[i] = carry + e;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) total[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_clear_kernel(uint4* __restrict__ p, long long n) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// MSB-first bit writer into 32-bit words: bit p of the stream is bit 31 - (p & 31) of word p >> 5
+struct WordSink {
+    uint32_t* w;
+    uint64_t acc = 0;
+    int fill;
+    bool first = true;
+    __device__ __forceinline__ WordSink(uint32_t* words, int bitpos) : w(words + (bitpos >> 5)), fill(bitpos & 31) {}
+    __device__ __forceinline__ void put(uint32_t bits, int n) {
+        acc |= (uint64_t)bits << (64 - fill - n);  // fill < 32, 1 <= n <= 27
+        fill += n;
+        if (fill >= 32) {
+            const uint32_t word = (uint32_t)(acc >> 32);
+            if (first) atomicOr(w, word);  // may share its leading bits with the previous block
+            else *w = word;                // all 32 bits are this block's
+            first = false;
+            ++w;
+            acc <<= 32;
+            fill -= 32;
+        }
+    }
+    __device__ __forceinline__ void flush() {
+        if (fill > 0) atomicOr(w, (uint32_t)(acc >> 32));
+    }
+};
+
+__global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(const int16_t* __restrict__ coef, int B, int nb,
+                                                            const int* __restrict__ offs, uint32_t* __restrict__ words,
+                                                            int nwords) {
+    const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (gid >= (long long)B * nb) return;
+    const int blk = (int)(gid % nb);
+    const int b = (int)(gid / nb);
+    const int16_t* img = coef + (gid - blk) * 64;
+    WordSink s(words + (long long)b * nwords, offs[gid]);
+    encode_block(img + (long long)blk * 64, pred_dc(img, blk), d_huff, (blk & 3) < 2 ? 0 : 1, s);
+    s.flush();
+}
+
+// the four stream bytes of word wi as values 0..255, or -1 past the end; the last byte is padded with 1-bits
+__device__ __forceinline__ void stream_bytes(const uint32_t* words, int wi, int nbytes, int totalbits, int* by) {
+    const uint32_t w = (long long)wi * 4 < nbytes ? words[wi] : 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = wi * 4 + j;
+        int v = (int)((w >> (24 - 8 * j)) & 255u);
+        if (k == nbytes - 1) v |= (1 << (nbytes * 8 - totalbits)) - 1;
+        by[j] = k < nbytes ? v : -1;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_ff_count_kernel(const uint32_t* __restrict__ words, int nwords,
+                                                                const int* __restrict__ total, int nchunks,
+                                                                int* __restrict__ ff) {
+    __shared__ int sh[kThreads];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int totalbits = total[b], nbytes = (totalbits + 7) >> 3;
+    if ((long long)chunk * kChunkWords * 4 >= nbytes) {  // uniform over the work-group
+        if (threadIdx.x == 0) ff[b * nchunks + chunk] = 0;
+        return;
+    }
+    int by[4];
+    stream_bytes(words + (long long)b * nwords, chunk * kChunkWords + threadIdx.x, nbytes, totalbits, by);
+    const int c = (by[0] == 255) + (by[1] == 255) + (by[2] == 255) + (by[3] == 255);
+    int sum;
+    block_excl_scan(c, sh, sum);
+    if (threadIdx.x == 0) ff[b * nchunks + chunk] = sum;
+}
+
+// one work-group per image: chunk 0xFF counts -> exclusive offsets in place; sizes[b]; header and EOI of the file
+__global__ __launch_bounds__(kThreads) void jpeg_ff_scan_kernel(int* __restrict__ ff, int nchunks,
+                                                               const int* __restrict__ total, int* __restrict__ sizes,
+                                                               uint8_t* __restrict__ files, long long stride,
+                                                               HeaderArg hdr) {
+    __shared__ int sh[kThreads];
+    const int b = blockIdx.x;
+    int* p = ff + (long long)b * nchunks;
+    int carry = 0;
+    for (int base = 0; base < nchunks; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const int x = i < nchunks ? p[i] : 0;
+        int sum;
+        const int e = block_excl_scan(x, sh, sum);
+        if (i < nchunks) p[i] = carry + e;
+        carry += sum;
+    }
+    const int nbytes = (total[b] + 7) >> 3;
+    const int body = nbytes + carry;
+    if (threadIdx.x == 0) sizes[b] = kHeaderBytes + body + 2;
+    if (files) {
+        uint8_t* f = files + (long long)b * stride;
+        for (int i = threadIdx.x; i < kHeaderBytes; i += kThreads) f[i] = hdr.b[i];
+        if (threadIdx.x == 0) {
+            f[kHeaderBytes + body] = 0xFF;
+            f[kHeaderBytes + body + 1] = 0xD9;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_ff_emit_kernel(const uint32_t* __restrict__ words, int nwords,
+                                                               const int* __restrict__ total,
+                                                               const int* __restrict__ ffoff, int nchunks,
+                                                               uint8_t* __restrict__ files, long long stride) {
+    __shared__ int sh[kThreads];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int totalbits = total[b], nbytes = (totalbits + 7) >> 3;
+    if ((long long)chunk * kChunkWords * 4 >= nbytes) return;  // uniform over the work-group
+    const int wi = chunk * kChunkWords + threadIdx.x;
+    int by[4];
+    stream_bytes(words + (long long)b * nwords, wi, nbytes, totalbits, by);
+    const int c = (by[0] == 255) + (by[1] == 255) + (by[2] == 255) + (by[3] == 255);
+    int sum;
+    int before = ffoff[b * nchunks + chunk] + block_excl_scan(c, sh, sum);
+    uint8_t* f = files + (long long)b * stride + kHeaderBytes;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (by[j] < 0) break;
+        const long long o = (long long)wi * 4 + j + before;
+        f[o] = (uint8_t)by[j];
+        if (by[j] == 255) {
+            f[o + 1] = 0;
+            ++before;
+        }
+    }
+}
+
+static int check_shape(const char* what, int B, int H, int W) {
+    HY_REQUIRE(B >= 1 && H >= 8 && W >= 16 && H % 8 == 0 && W % 16 == 0 && H <= 65528 && W <= 65520, HYRES_E_SHAPE,
+               "%s: B >= 1, H %% 8 == 0, W %% 16 == 0, H, W < 65536 (got %d x %d x %d)", what, B, H, W);
+    HY_REQUIRE((long long)blocks_per_image(H, W) * kMaxBlockBits < (1LL << 31) && (long long)B * H * W < (1LL << 31),
+               HYRES_E_SHAPE, "%s: %d x %d x %d is too large", what, B, H, W);
+    return ok();
+}
+
+}  // namespace jpeg
+}  // namespace hyres
+
+using namespace hyres;
+using namespace hyres::jpeg;
+
+extern "C" {
+
+int hyres_jpeg_quant_tables(int quality, unsigned char* lum, unsigned char* chr) {
+    HY_REQUIRE(lum && chr, HYRES_E_ARG, "jpeg_quant_tables: NULL");
+    quant_tables_zigzag(quality, lum, chr);
+    return ok();
+}
+
+long long hyres_jpeg_workspace_bytes(int B, int H, int W) {
+    if (check_shape("jpeg_workspace_bytes", B, H, W)) return -1;
+    return make_layout(B, H, W).end;
+}
+
+long long hyres_jpeg_stream_bytes(int H, int W) {
+    if (check_shape("jpeg_stream_bytes", 1, H, W)) return -1;
+    // header + the entropy segment at kMaxBlockBits per block with every byte stuffed + EOI
+    return align256(kHeaderBytes + 2LL * make_layout(1, H, W).nwords * 4 + 2);
+}
+
+int hyres_jpeg_roundtrip(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                         unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                         hyres_stream_t s) {
+    HY_REQUIRE(x && decoded && sizes, HYRES_E_ARG, "jpeg_roundtrip: NULL");
+    int rc = check_shape("jpeg_roundtrip", B, H, W);
+    if (rc) return rc;
+    const Layout L = make_layout(B, H, W);
+    HY_REQUIRE(ws && ws_bytes >= L.end, HYRES_E_WORKSPACE, "jpeg_roundtrip: workspace %lld < %lld", ws_bytes, L.end);
+    HY_REQUIRE(aligned16(ws) && aligned16(decoded), HYRES_E_ALIGN, "jpeg_roundtrip: alignment");
+    HY_REQUIRE(!files || file_stride >= hyres_jpeg_stream_bytes(H, W), HYRES_E_WORKSPACE,
+               "jpeg_roundtrip: file stride %lld < %lld", file_stride, hyres_jpeg_stream_bytes(H, W));
+    char* base = (char*)ws;
+    int16_t* coef = (int16_t*)(base + L.coef);
+    uint8_t *yp = (uint8_t*)(base + L.yp), *cbp = (uint8_t*)(base + L.cbp), *crp = (uint8_t*)(base + L.crp);
+    int *bits = (int*)(base + L.bits), *total = (int*)(base + L.total), *ff = (int*)(base + L.ff);
+    uint32_t* words = (uint32_t*)(base + L.words);
+    hipStream_t st = as_stream(s);
+    const QuantTables Q = quant_tables_natural(quality);
+    HeaderArg hdr;
+    uint8_t z[2][64];
+    quant_tables_zigzag(quality, z[0], z[1]);
+    build_header(z[0], z[1], H, W, hdr.b);
+
+    // cleared by a kernel, not hipMemsetAsync: captured into a graph, the memset cleared the buffer for the first
+    // replay only, and later replays ORed their bits into the previous stream
+    const long long nvec = (long long)B * L.nwords / 4;  // nwords is a multiple of 256
+    hipLaunchKernelGGL(jpeg_clear_kernel, dim3(ceil_div(nvec, kThreads)), dim3(kThreads), 0, st, (uint4*)words, nvec);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_clear"))) return rc;
+    const int gblk = ceil_div((long long)B * L.nb, kThreads);
+    hipLaunchKernelGGL(jpeg_blocks_kernel, dim3(gblk), dim3(kThreads), 0, st, x, B, H, W, Q, coef, yp, cbp, crp);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_blocks"))) return rc;
+    hipLaunchKernelGGL(jpeg_decode_kernel, dim3(ceil_div((long long)B * H * (W / 2), kThreads)), dim3(kThreads), 0, st,
+                       yp, cbp, crp, B, H, W, decoded);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_decode"))) return rc;
+    hipLaunchKernelGGL(jpeg_count_kernel, dim3(gblk), dim3(kThreads), 0, st, coef, B, L.nb, bits);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_count"))) return rc;
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(B), dim3(kThreads), 0, st, bits, L.nb, total);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_scan"))) return rc;
+    hipLaunchKernelGGL(jpeg_pack_kernel, dim3(gblk), dim3(kThreads), 0, st, coef, B, L.nb, bits, words, L.nwords);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_pack"))) return rc;
+    hipLaunchKernelGGL(jpeg_ff_count_kernel, dim3(L.nchunks, B), dim3(kThreads), 0, st, words, L.nwords, total,
+                       L.nchunks, ff);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_ff_count"))) return rc;
+    hipLaunchKernelGGL(jpeg_ff_scan_kernel, dim3(B), dim3(kThreads), 0, st, ff, L.nchunks, total, sizes, files,
+                       file_stride, hdr);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_ff_scan"))) return rc;
+    if (files) {
+        hipLaunchKernelGGL(jpeg_ff_emit_kernel, dim3(L.nchunks, B), dim3(kThreads), 0, st, words, L.nwords, total, ff,
+                           L.nchunks, files, file_stride);
+        if ((rc = HY_LAUNCH_CHECK("jpeg_ff_emit"))) return rc;
+    }
+    return ok();
+}
+
+int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                              unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                              hyres_stream_t s) {
+    (void)ws, (void)ws_bytes, (void)s;
+    HY_REQUIRE(x && decoded && sizes, HYRES_E_ARG, "jpeg_roundtrip_host: NULL");
+    int rc = check_shape("jpeg_roundtrip_host", B, H, W);
+    if (rc) return rc;
+    HY_REQUIRE(!files || file_stride >= hyres_jpeg_stream_bytes(H, W), HYRES_E_WORKSPACE,
+               "jpeg_roundtrip_host: file stride %lld < %lld", file_stride, hyres_jpeg_stream_bytes(H, W));
+    std::vector<uint8_t> f;
+    const long long img = 3LL * H * W;
+    for (int b = 0; b < B; ++b) {
+        sizes[b] = roundtrip_image_host(x + b * img, H, W, quality, decoded + b * img, &f);
+        if (files) std::memcpy(files + b * file_stride, f.data(), f.size());
+    }
+    return ok();
+}
+
+}  // extern "C"

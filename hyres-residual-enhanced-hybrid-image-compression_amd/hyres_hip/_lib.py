@@ -144,7 +144,12 @@ _SIGS = {
     "hyres_pmf_to_quantized_cdf": (_I, [_P, _I, _I, _P]),
     "hyres_rans_encode_with_indexes": (_I, [_P, _P, _LL, _P, _I, _P, _P, _I, _P, _LL, ctypes.POINTER(_LL)]),
     "hyres_rans_decode_with_indexes": (_I, [_P, _LL, _P, _LL, _P, _I, _P, _P, _I, _P]),
-    "hyres_ckbd_anchor_fwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "hyres_jpeg_quant_tables": (_I, [_I, _P, _P]),
+    "hyres_jpeg_workspace_bytes": (_LL, [_I, _I, _I]),
+    "hyres_jpeg_stream_bytes": (_LL, [_I, _I]),
+    "hyres_jpeg_roundtrip": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P]),
+    "hyres_jpeg_roundtrip_host": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P]),
+    "hyres_ckbd_anchor_fwd":(_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "hyres_ckbd_nonanchor_gc_fwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                          _I, _I, _I, _I, _P]),
     "hyres_ckbd_gc_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),

@@ -91,7 +91,10 @@ class CapturedStep:
         dev = x.device
         self.x = x.detach().clone()
         self.jpeg = jpeg_decoded.detach().clone()
-        self.bpp = torch.full((), float(jpeg_bpp), dtype=torch.float32, device=dev)
+        if isinstance(jpeg_bpp, torch.Tensor):  # the device JPEG codec's 0-dim tensor: no host read
+            self.bpp = jpeg_bpp.detach().to(device=dev, dtype=torch.float32).reshape(()).clone()
+        else:
+            self.bpp = torch.full((), float(jpeg_bpp), dtype=torch.float32, device=dev)
         self.noisequant = noisequant
         self.criterion = criterion
         _prepare_noise(net, dev)
@@ -252,7 +255,10 @@ class CapturedStep:
         if jpeg_decoded is not None:
             self.jpeg.copy_(jpeg_decoded, non_blocking=True)
         if jpeg_bpp is not None:
-            self.bpp.fill_(float(jpeg_bpp))
+            if isinstance(jpeg_bpp, torch.Tensor):
+                self.bpp.copy_(jpeg_bpp.reshape(()), non_blocking=True)
+            else:
+                self.bpp.fill_(float(jpeg_bpp))
         last = len(self.graphs) - 1
         for i, g in enumerate(self.graphs):
             g.replay()

@@ -1,8 +1,9 @@
 """ResidualJPEGCompression (models/hyres.py:9-181) — the drop-in boundary of this build.
 
 forward(x [B,3,H,W] in [0,1], noisequant=False) -> {'x_hat', 'likelihoods': {'y','z'}, 'jpeg_bpp_loss',
-'jpeg_decoded', 'residual', 'residual_hat'} exactly as the reference (:70-77).  The JPEG base layer stays
-a host stage (libjpeg-turbo); everything after the host->device copy — residual, LightWeightCheckerboard,
+'jpeg_decoded', 'residual', 'residual_hat'} exactly as the reference (:70-77).  The JPEG base layer is
+a host stage (libjpeg-turbo) by default, or the bit-exact device codec (hyres_hip/jpeg_device.py) when
+``TurboJPEGCompression.device_codec`` is on; everything after the host->device copy — residual, LightWeightCheckerboard,
 x_hat_initial, MultiScaleRefine, clamp — is ONE HIP tape (forward and backward on MI355X).
 
 Fixed reference bugs (documented in DESIGN.md):
@@ -12,10 +13,12 @@ Fixed reference bugs (documented in DESIGN.md):
 """
 from __future__ import annotations
 
+import io
 from typing import Optional, Tuple
 
 import torch
 
+from hyres_hip import jpeg_device
 from hyres_hip import ops as O
 from hyres_hip import refine_ops as R
 from hyres_hip import runtime
@@ -75,6 +78,10 @@ class ResidualJPEGCompression(CompressionModel):
     def forward(self, x, noisequant=False, jpeg: Optional[Tuple[torch.Tensor, float]] = None):
         """models/hyres.py:23-77.  ``jpeg=(decoded, bpp)`` skips the host JPEG stage (precomputed)."""
         device = next(self.parameters()).device
+        if jpeg is None and self.jpeg.on_device(x) and x.device == device:
+            # device codec: no copy to the host, no second upload, jpeg_bpp stays a device tensor
+            jpeg_decoded, jpeg_bpp = self.jpeg(x.detach())
+            return self.forward_device(x, jpeg_decoded, jpeg_bpp, noisequant)
         if jpeg is None:
             x_cpu = x.detach().cpu() if x.device.type != "cpu" else x
             jpeg_decoded_cpu, jpeg_bpp = self.jpeg(x_cpu)
@@ -89,9 +96,14 @@ class ResidualJPEGCompression(CompressionModel):
     def compress(self, x):
         """models/hyres.py:78-98: JPEG buffers (host) + the residual model's rANS strings."""
         device = next(self.parameters()).device
-        x_cpu = x.detach().cpu() if x.device.type != "cpu" else x
-        jpeg_buffers = self.jpeg.compress(x_cpu)
-        jpeg_decoded = self.jpeg.decompress(jpeg_buffers, device)
+        if self.jpeg.on_device(x) and x.device == device:
+            # device codec: the decoded base layer of the round trip is what the decoder will reconstruct
+            jpeg_decoded, datas = jpeg_device.encode(x.detach(), self.jpeg.quality)
+            jpeg_buffers = [io.BytesIO(d) for d in datas]
+        else:
+            x_cpu = x.detach().cpu() if x.device.type != "cpu" else x
+            jpeg_buffers = self.jpeg.compress(x_cpu)
+            jpeg_decoded = self.jpeg.decompress(jpeg_buffers, device)
         residual = x.to(device) - jpeg_decoded
         residual_compressed = self.residual_model.compress(residual)
         residual_compressed["jpeg_buffers"] = jpeg_buffers

@@ -12,6 +12,11 @@ The hard-coded ``lib_path`` of the reference (:12) is replaced by the library's 
 (Pillow's coder holds the GIL, so threads do not scale), else by a thread pool (PyTurboJPEG releases the
 GIL); ``prefetch`` overlaps the next batch's JPEG with the device step.  This is the host-side half of the
 multi-GPU scaling story.
+
+Opt-in device codec: ``device_codec=True`` (or HYRES_JPEG_CODEC=device) runs the round trip of a supported GPU
+tensor (3-channel fp32, H % 8 == 0, W % 16 == 0) as HIP kernels (hyres_hip/jpeg_device.py), bit-exact with the
+host path: no device-to-host copy, no second upload, ``jpeg_bpp`` a 0-dim device tensor.  Everything else (CPU
+tensors, grey input, ragged sizes, ``decompress`` of foreign bytes) keeps the host path; the default is ``host``.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from hyres_hip import jpeg_host
+from hyres_hip import jpeg_device, jpeg_host
 
 try:  # pragma: no cover - not installed in this image
     from turbojpeg import TurboJPEG as _TurboJPEG  # type: ignore
@@ -64,9 +69,16 @@ class TurboJPEGCompression(nn.Module):
     releases the GIL); ``prefetch(x)`` starts the next batch's round trip in the background so a training
     loop overlaps the host JPEG stage with the device step (src/utils/engine.py does this)."""
 
-    def __init__(self, quality=25, lib_path: Optional[str] = None, workers: Optional[int] = None):
+    def __init__(self, quality=25, lib_path: Optional[str] = None, workers: Optional[int] = None,
+                 device_codec: Optional[bool] = None):
         super().__init__()
         self.quality = quality
+        if device_codec is None:
+            codec = os.environ.get("HYRES_JPEG_CODEC", "host")
+            if codec not in ("host", "device"):
+                raise ValueError(f"HYRES_JPEG_CODEC={codec!r}: 'host' or 'device'")
+            device_codec = codec == "device"
+        self.device_codec = bool(device_codec)
         lib_path = lib_path or os.environ.get("HYRES_TURBOJPEG_LIB")
         if _TurboJPEG is not None:
             self.jpeg = _TurboJPEG(lib_path) if lib_path else _TurboJPEG()
@@ -91,7 +103,13 @@ class TurboJPEGCompression(nn.Module):
             self._pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="hyres-jpeg")
         return list(self._pool.map(fn, items))
 
+    def on_device(self, x: torch.Tensor) -> bool:
+        """This input takes the device codec (else the host path, unchanged)."""
+        return self.device_codec and jpeg_device.supported(x)
+
     def compress(self, x: torch.Tensor) -> List[io.BytesIO]:
+        if self.on_device(x):
+            return [io.BytesIO(d) for d in jpeg_device.encode(x, self.quality)[1]]  # the only device-to-host copy
         imgs = _to_uint8_batch(x.detach().cpu())
         datas = self._map(lambda im: self.jpeg.encode(im, quality=self.quality), list(imgs))
         return [io.BytesIO(d) for d in datas]
@@ -140,6 +158,8 @@ class TurboJPEGCompression(nn.Module):
         stay in flight (oldest dropped first); prefetching a batch that is already pending is a no-op."""
         if x.device.type != "cpu":
             return
+        if self.device_codec and torch.cuda.is_available() and jpeg_device.supported_shape(x):
+            return  # the device codec codes this batch on the GPU: no host work to start
         key = self._key(x)
         if key in self._pending:
             return
@@ -152,7 +172,11 @@ class TurboJPEGCompression(nn.Module):
         self._pending[key] = (weakref.ref(x), self._bg.submit(self._roundtrip, x.detach()))
 
     def forward(self, x: torch.Tensor):
-        """(decoded [N,3,H,W] on x.device, jpeg_bpp = total bytes * 8 / (N*H*W))  (:62-77)."""
+        """(decoded [N,3,H,W] on x.device, jpeg_bpp = total bytes * 8 / (N*H*W))  (:62-77); with the device codec
+        on a supported GPU tensor ``jpeg_bpp`` is a 0-dim device tensor and nothing leaves the GPU."""
+        if self.on_device(x):
+            decoded, sizes = jpeg_device.roundtrip(x, self.quality)
+            return decoded, jpeg_device.bpp(sizes, x)
         device = x.device
         ent = self._pending.pop(self._key(x), None) if x.device.type == "cpu" else None
         fut = ent[1] if ent is not None and ent[0]() is x else None

@@ -14,7 +14,9 @@ Differences from the reference, by design:
     (hyres_hip.optim.DeviceGradScaler), so there is still no per-step host sync.  The reference's NaN
     warning is printed when the metrics are drained;
   * the next batch's host JPEG round trip is started in the background before the current step
-    (TurboJPEGCompression.prefetch), so the host JPEG stage overlaps the device step;
+    (TurboJPEGCompression.prefetch), so the host JPEG stage overlaps the device step; with the opt-in device
+    codec (HYRES_JPEG_CODEC=device) the round trip runs as HIP kernels on the stream right before the replay and
+    prefetch does nothing;
   * forward + RD loss + backward replay as a HIP graph (hyres_hip.graphs.CapturedStep, one capture per
     batch shape / noisequant / precision, taken on an accumulation boundary); the host JPEG stage, the
     H2D copies, the gradient all-reduce (after the replay in 32 MB buckets, as bench.py's N > 1 default),
@@ -98,9 +100,13 @@ class _GraphedStep:
         cap = self.caps.get(key)
         if cap is None and not boundary_start:
             return None  # capturing zeroes the gradients: only where no partial accumulation exists
-        dec, bpp = self.model.jpeg(d)  # host JPEG round trip (prefetched in the background)
         x = d.to(self.device)
-        jd = dec.to(self.device)
+        jpeg = self.model.jpeg
+        if getattr(jpeg, "device_codec", False) and jpeg.on_device(x):
+            jd, bpp = jpeg(x)  # device JPEG round trip, eagerly on the stream ahead of the replay; bpp a device tensor
+        else:
+            dec, bpp = jpeg(d)  # host JPEG round trip (prefetched in the background)
+            jd, bpp = dec.to(self.device), float(bpp)
         if self.scaler is not None:
             torch.mul(self.scaler.scale, 1.0 / self.accum, out=self.ls)
         if cap is None:
@@ -111,7 +117,7 @@ class _GraphedStep:
             err = None
             try:
                 split = ("hyper",) if reducer is not None and os.environ.get("HYRES_DIST_SPLIT", "1") == "1" else ()
-                cap = CapturedStep(self.model, x, jd, float(bpp), noisequant=noisequant, criterion=self.criterion,
+                cap = CapturedStep(self.model, x, jd, bpp, noisequant=noisequant, criterion=self.criterion,
                                    zero_grad=self.zero_grad, amp=self.amp, loss_scale=self.ls,
                                    capture_error_mode="thread_local" if reducer is not None else "global",
                                    split_at=split)
@@ -130,7 +136,7 @@ class _GraphedStep:
             self.caps[key] = cap
         self.last = cap
         between = reducer.launch_segments if (reducer is not None and boundary_end and cap.split_at) else None
-        return cap.replay(x, jd, float(bpp), between=between)[1]
+        return cap.replay(x, jd, bpp, between=between)[1]
 
     def close(self) -> None:
         """Release every captured graph explicitly (end of the epoch), not from a finalizer."""
@@ -214,6 +220,8 @@ def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer
             n_img = len(d)
         else:
             with amp():
+                if getattr(jpeg, "device_codec", False):
+                    d = d.to(device)  # the device JPEG codec takes the batch where the model runs
                 out_net = model(d, noisequant)
                 d = d.to(device)
                 out_criterion = criterion(out_net, d)

@@ -625,6 +625,30 @@ int hyres_rans_decode_with_indexes(const unsigned char* in, long long in_len, co
                                    const int* cdfs, int cdf_stride, const int* cdf_sizes, const int* offsets,
                                    int ncdf, int* symbols_out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* JPEG 4:2:2 base layer: bit-exact with libjpeg-turbo at PyTurboJPEG's defaults */
+/* ------------------------------------------------------------------------------------------ */
+/* libjpeg's quality-scaled baseline quantisation tables (entries 1..255) in zigzag order, i.e. the two DQT
+ * payloads of the file (host) */
+int hyres_jpeg_quant_tables(int quality, unsigned char* lum64, unsigned char* chr64);
+/* workspace of hyres_jpeg_roundtrip for a [B,3,H,W] batch (H % 8 == 0, W % 16 == 0), or -1 (host) */
+long long hyres_jpeg_workspace_bytes(int B, int H, int W);
+/* bytes one image's file can take at most: the 623-byte header, the entropy segment at the worst case of 1664
+ * bits per 8x8 block with every byte stuffed, EOI; the minimum ``file_stride`` below (host) */
+long long hyres_jpeg_stream_bytes(int H, int W);
+/* Encode -> decode round trip of x [B,3,H,W] fp32 (channel 0 read as B; bytes = (clamp(x,0,1)*255) truncated):
+ * decoded [B,3,H,W] fp32 = decoded byte / 255, sizes[b] = byte count of image b's file, and if files != NULL the
+ * file itself at files + b * file_stride. All device pointers; kernels on ``s`` only — no host sync, allocation
+ * or copy, so the call can be captured into a graph. */
+int hyres_jpeg_roundtrip(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                         unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                         hyres_stream_t s);
+/* the same round trip on host memory with the same arithmetic (csrc/jpeg_core.h); ws and s are ignored, no GPU
+ * call is made (host) */
+int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                              unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                              hyres_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
