@@ -4,6 +4,8 @@ Per image (as the reference, :53-150): ``model.compress(x)`` -> ``model.decompre
 the rANS string lengths, JPEG bpp from the real JPEG bytes, enc/dec time from the models' own timers.
 PSNR = 10*log10(1/mse) — the reference's formula at :123-125, ``-10*log10(mse*255^2)``, is wrong (it
 would report a large negative number); fixed here and documented in DESIGN.md.
+MS-SSIM (:127-132) comes from the HIP metric (hyres_hip.metrics.ms_ssim == pytorch_msssim.ms_ssim(x, x_hat,
+data_range=1.0)); an image with min(H, W) <= 160 is too small for five levels and keeps 0.0.
 CSV columns are the reference's (:232-246)."""
 import argparse
 import csv
@@ -17,6 +19,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from hyres_hip.metrics import min_side, ms_ssim
 from models import LightWeightCheckerboard, ResidualJPEGCompression
 from src.utils import load_checkpoint
 
@@ -74,13 +77,14 @@ def process_image(model, img_path, output_dir, device, save_components=False):
     total_bpp = jpeg_bpp + y_bpp + z_bpp
     mse = torch.nn.functional.mse_loss(x, out_dec["x_hat"]).item()
     psnr = 10 * math.log10(1.0 / max(mse, 1e-12))
+    msssim = ms_ssim(x, out_dec["x_hat"], data_range=1.0).item() if min(H, W) > min_side(5) else 0.0
     print(f"Processed {img_path}")
     print(f"Total bpp: {total_bpp:.4f} (JPEG: {jpeg_bpp:.4f}, Y: {y_bpp:.5f}, Z: {z_bpp:.5f})")
     print(f"MSE: {mse * 255 ** 2:.4f})")
-    print(f"PSNR: {psnr:.2f} dB, MS-SSIM: 0.0000")
+    print(f"PSNR: {psnr:.2f} dB, MS-SSIM: {msssim:.4f}")
     print(f"Encoding time: {enc_time:.4f}s, Decoding time: {dec_time:.4f}s")
     return {"filename": os.path.basename(img_path), "total_bpp": total_bpp, "jpeg_bpp": jpeg_bpp, "y_bpp": y_bpp,
-            "z_bpp": z_bpp, "mse": mse * 255 ** 2, "psnr": psnr, "ms_ssim": 0.0, "enc_time": enc_time,
+            "z_bpp": z_bpp, "mse": mse * 255 ** 2, "psnr": psnr, "ms_ssim": msssim, "enc_time": enc_time,
             "dec_time": dec_time}
 
 
@@ -114,6 +118,7 @@ def main(argv):
         print(f"Total bpp: {avg['total_bpp']:.4f} (JPEG: {avg['jpeg_bpp']:.4f}, Y: {avg['y_bpp']:.5f}, "
               f"Z: {avg['z_bpp']:.5f})")
         print(f"PSNR: {avg['psnr']:.2f} dB")
+        print(f"MS-SSIM: {avg['ms_ssim']:.4f}")
         with open(os.path.join(args.output, "metrics.csv"), "w", newline="") as f:
             w = csv.writer(f)
             w.writerow(["filename", "total_bpp", "jpeg_bpp", "y_bpp", "z_bpp", "mse", "psnr", "ms_ssim",

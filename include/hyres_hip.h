@@ -649,6 +649,26 @@ int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, 
                               unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
                               hyres_stream_t s);
 
+/* ------------------------------------------------------------------------------------------ */
+/* MS-SSIM / SSIM metric: pytorch_msssim's ms_ssim at its defaults (11-tap sigma-1.5 window, valid filtering,     */
+/* K = (0.01, 0.03), 2x2 average pooling with padding side % 2 between levels)                                   */
+/* ------------------------------------------------------------------------------------------ */
+/* workspace of hyres_msssim for two [B,C,H,W] batches, or -1 on a bad shape (host) */
+long long hyres_msssim_workspace_bytes(int B, int C, int H, int W, int levels);
+/* x, y: contiguous NCHW fp32 on the device; 1 <= levels <= 5 and min(H, W) > 10 * 2^(levels - 1) (HYRES_E_SHAPE
+ * otherwise); weights: ``levels`` floats on the HOST, passed to the kernel by value. out[b] = mean over c of
+ * prod_l relu(m[l][b][c])^weights[l], where m is the spatial mean of cs_map for l < levels - 1 and of ssim_map for
+ * the last level; per_level (may be NULL) receives m itself, [levels][B][C], before the relu — levels = 1 gives
+ * plain SSIM. levels + 1 launches on ``s``; no host sync, allocation, copy, memset or atomic, every sum in a fixed
+ * order: capture-legal, and the same input gives the same bits, alone or inside a batch. */
+int hyres_msssim(const float* x, const float* y, int B, int C, int H, int W, int levels, const float* weights,
+                 float data_range, float* out, float* per_level, void* ws, long long ws_bytes, hyres_stream_t s);
+/* the same on host memory with the same arithmetic (csrc/msssim_core.h); ws and s are ignored, no GPU call is made
+ * (host) */
+int hyres_msssim_host(const float* x, const float* y, int B, int C, int H, int W, int levels, const float* weights,
+                      float data_range, float* out, float* per_level, void* ws, long long ws_bytes,
+                      hyres_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
