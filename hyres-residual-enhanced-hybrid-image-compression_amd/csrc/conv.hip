@@ -13,6 +13,7 @@
 //     consecutive MFMA steps (conflict-free with the 36-float row pitch).
 // Weight gradients use a second kernel (P^T Q over pixels, split-K slabs + deterministic reduce).
 #include "conv_common.h"
+#include <limits>
 
 namespace hyres {
 
@@ -1748,7 +1749,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const ConvArgs a
 // layout (lane (r, h): pixel p0 + r, channels 16j + 8h .. + 7, one 16-byte load per k-step) with a rolling prefetch
 // of the next tile, and the product is formed transposed (C^T = W X^T) so each lane's accumulator holds 4 consecutive
 // channels of one pixel. Layers with a streamed epilogue operand (residual, ReLU mask, old y) stay on the tiles
-// (measured: stream_h_nt). Arithmetic: fp16 operands, fp32 accumulation, fp32 epilogue, one rounding at the fp16
+// (measured: stream_h_cfg). Arithmetic: fp16 operands, fp32 accumulation, fp32 epilogue, one rounding at the fp16
 // store — the tiled f16 kernel's, in the same K order.
 typedef _Float16 half8s_t __attribute__((ext_vector_type(8)));
 
@@ -2655,8 +2656,8 @@ static bool narrow_ok(const hyres_conv_geom* g) {
 }
 
 template <int CO>
-static void launch_narrow(const ConvArgs& a, dim3 grid, hipStream_t st) {
-    if (narrow_strip_ok(&a.g)) {  // hyres_conv_tuning key 13 (default 1)
+static void launch_narrow(const ConvArgs& a, bool strip, dim3 grid, hipStream_t st) {
+    if (strip) {  // narrow_strip_ok: hyres_conv_tuning key 13 (default 1)
         const bool h = (a.e.io_f16 & HYRES_IO_X16) != 0;
         if (a.g.Ci == 64) {
             if (h) hipLaunchKernelGGL((conv_narrow_strip_kernel<CO, 1, true>), grid, dim3(256), 0, st, a);
@@ -2765,108 +2766,6 @@ __global__ void weight_prep_kernel(const PrepArgs a) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-template <int TM, int TN, int WM_, int WN_>
-static int launch_fwd(const ConvArgs& a, int mode, hipStream_t st) {
-    constexpr int BM = 32 * TM * WM_, BN = 32 * TN * WN_;
-    dim3 grid(ceil_div(a.M, BM), ceil_div(a.g.Co, BN), a.g.nphase * a.nsplit);
-    if (a.xcd) grid = dim3(grid.x * grid.y, 1, grid.z);
-    if (a.e.io_f16 & 3) {
-        const int io = a.e.io_f16 & 3;
-#define HY_H(MODE_, SPLIT_)                                                                                       \
-    {                                                                                                            \
-        if (io == 1) hipLaunchKernelGGL((conv_fwd_h_kernel<TM, TN, WM_, WN_, MODE_, SPLIT_, 1>), grid, dim3(256), 0, st, a); \
-        else if (io == 2) hipLaunchKernelGGL((conv_fwd_h_kernel<TM, TN, WM_, WN_, MODE_, SPLIT_, 2>), grid, dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((conv_fwd_h_kernel<TM, TN, WM_, WN_, MODE_, SPLIT_, 3>), grid, dim3(256), 0, st, a); \
-    }
-        if (mode == 2) {
-            if (a.nsplit > 1) hipLaunchKernelGGL((conv_fwd_h_kernel<TM, TN, WM_, WN_, 2, true, 2>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_fwd_h_kernel<TM, TN, WM_, WN_, 2, false, 2>), grid, dim3(256), 0, st, a);
-        } else if (a.nsplit > 1) {
-            if (mode == 0) HY_H(0, true) else HY_H(1, true)
-        } else {
-            if (mode == 0) HY_H(0, false) else HY_H(1, false)
-        }
-#undef HY_H
-        return HY_LAUNCH_CHECK("conv_fwd_h_kernel");
-    }
-    if (a.e.f16_operands && mode != 2) {
-        if (a.nsplit > 1) {
-            if (mode == 0) hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 0, true, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 1, true, true>), grid, dim3(256), 0, st, a);
-        } else {
-            if (mode == 0) hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 0, false, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 1, false, true>), grid, dim3(256), 0, st, a);
-        }
-        return HY_LAUNCH_CHECK("conv_fwd_kernel(f16)");
-    }
-    if (g_tune[7] == 1 && mode != 2) {  // fp32 GEMM on the bf16 MFMA (bf16x6)
-        if constexpr (TM == 1 && TN == 1 && WM_ == 2 && WN_ == 2) {
-            // double-buffered staging (key 20 = 1, or -1: on for the <= 16384-pixel grids). Isolated it wins at 32^2
-            // (3x3 96 -> 96 39.6 -> 37.3 us, 1x1 192 -> 96 13.9 -> 13.1 us) and loses on the larger-K 64^2 / 5x5 layers
-            // (+2..5 %: the 49 KB of LDS cost the 4th block per CU, profiles/r6m_b6db.txt); in the graphed step the
-            // small-grid rule measured 0.2-0.3 ms SLOWER (profiles/r6n_b6db_step_ab.txt: those layers run beside the
-            // branch streams' kernels), so the default is off
-            if (g_tune[20] == 1 || (g_tune[20] < 0 && a.M <= 16384)) {
-                if (a.nsplit > 1) {
-                    if (mode == 0) hipLaunchKernelGGL((conv_fwd_b6db_kernel<1, 1, 2, 2, 0, true>), grid, dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((conv_fwd_b6db_kernel<1, 1, 2, 2, 1, true>), grid, dim3(256), 0, st, a);
-                } else {
-                    if (mode == 0) hipLaunchKernelGGL((conv_fwd_b6db_kernel<1, 1, 2, 2, 0, false>), grid, dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((conv_fwd_b6db_kernel<1, 1, 2, 2, 1, false>), grid, dim3(256), 0, st, a);
-                }
-                return HY_LAUNCH_CHECK("conv_fwd_b6db_kernel");
-            }
-        }
-        if (a.nsplit > 1) {
-            if (mode == 0) hipLaunchKernelGGL((conv_fwd_b6_kernel<TM, TN, WM_, WN_, 0, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_fwd_b6_kernel<TM, TN, WM_, WN_, 1, true>), grid, dim3(256), 0, st, a);
-        } else {
-            if (mode == 0) hipLaunchKernelGGL((conv_fwd_b6_kernel<TM, TN, WM_, WN_, 0, false>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_fwd_b6_kernel<TM, TN, WM_, WN_, 1, false>), grid, dim3(256), 0, st, a);
-        }
-        return HY_LAUNCH_CHECK("conv_fwd_b6_kernel");
-    }
-    // split-K launches are a separate instantiation (partials to the slab, no epilogue)
-    if (a.nsplit > 1) {
-        if (mode == 0) hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 0, true>), grid, dim3(256), 0, st, a);
-        else if (mode == 1) hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 1, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 2, true>), grid, dim3(256), 0, st, a);
-    } else {
-        if (mode == 0) hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 0, false>), grid, dim3(256), 0, st, a);
-        else if (mode == 1) hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 1, false>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_fwd_kernel<TM, TN, WM_, WN_, 2, false>), grid, dim3(256), 0, st, a);
-    }
-    return HY_LAUNCH_CHECK("conv_fwd_kernel");
-}
-
-// persistent grid: as many blocks as fit on the chip at once (occupancy query, cached per instantiation),
-// capped by blocks_per_cu (<= 0: no cap) and by the 32-pixel tiles available (4 per block)
-template <int NT, int KC>
-static int launch_stream_one(const ConvArgs& a, int blocks_per_cu, hipStream_t st) {
-    static int occ = -1;
-    if (occ < 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv1x1_stream_kernel<NT, KC>, 256, 0) != hipSuccess || n < 1)
-            n = 1;
-        occ = n;
-    }
-    const int per_cu = blocks_per_cu > 0 ? std::min(occ, blocks_per_cu) : occ;
-    const int blocks = std::max(1, std::min(ceil_div(ceil_div(a.M, 32), 4), 256 * per_cu));
-    if (a.e.f16_operands) hipLaunchKernelGGL((conv1x1_stream_kernel<NT, KC, true>), dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv1x1_stream_kernel<NT, KC>), dim3(blocks), dim3(256), 0, st, a);
-    return HY_LAUNCH_CHECK("conv1x1_stream_kernel");
-}
-
-static int launch_stream(const ConvArgs& a, int nt, int kc, int blocks_per_cu, hipStream_t st) {
-#define HY_STREAM(NT, KC) \
-    if (nt == NT && kc == KC) return launch_stream_one<NT, KC>(a, blocks_per_cu, st);
-    HY_STREAM(2, 8) HY_STREAM(2, 12) HY_STREAM(2, 16)
-    HY_STREAM(3, 8) HY_STREAM(3, 12) HY_STREAM(3, 16)
-    HY_STREAM(4, 8) HY_STREAM(4, 12) HY_STREAM(4, 16)
-    HY_STREAM(6, 8)
-#undef HY_STREAM
-    return set_error(HYRES_E_ARG, "conv1x1_stream: no instantiation for NT=%d KC=%d", nt, kc);
-}
 
 static void fill_taps(hyres_conv_geom* g, int p, int* tapcount, int K, int pad, int ph, int pw) {
     // sub-pixel phase (ph, pw) of a stride-2 transposed structure: taps kh with (ph+pad-kh) even
@@ -3060,19 +2959,48 @@ int hyres_conv_weight_prep_batch(const void* descs, int n, long long total, hyre
     return HY_LAUNCH_CHECK("weight_prep_batch_kernel");
 }
 
+}  // extern "C"
 
-// conv3x3_halo_f16_kernel applies (see above)
-static bool halo16_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
-    if (!e->f16_operands || g->nphase != 1 || g->ntaps != 9 || g->Ci % 32 != 0 || g->Co % 64 != 0) return false;
-    if (g->ish != 1 || g->isw != 1 || g->Hi != g->Ho || g->Wi != g->Wo || g->Hq != g->Ho || g->Wq != g->Wo) return false;
-    if (g->Wo % HALO_TW != 0 || e->square_input) return false;
-    for (int t = 0; t < 9; ++t)
-        if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return false;
-    return true;
-}
+// ------------------------------------------------------------------------------------------------
+// kernel choice: route() decides which kernel family runs; hyres_conv_forward launches what it says,
+// hyres_conv_kernel_name / hyres_conv_plan / hyres_conv_workspace_bytes report it
+// ------------------------------------------------------------------------------------------------
+enum class ConvFamily { NARROW, WRES32, WRES16, HALO16, STREAM_B6, STREAM, STREAM_HF, STREAM_H, TILES };
+// the implicit-GEMM tiles' kernel: fp16 X / Y, f16 operands, bf16x6 (double-buffered or not), fp32 MFMA / scalar loads
+enum class ConvGemm { H, F16, B6DB, B6, F32 };
 
-// conv3x3_wres_f16_kernel: the halo16 geometry with Ci == 64, enough 256-pixel tiles per block to amortise
-// the one-time weight conversion (>= 2 per block)
+struct ConvRoute {
+    ConvFamily family;
+    int mode;         // 0: vector loads (Ci % 32 == 0), 1: + squared input, 2: scalar loads
+    int tile;         // TILES (and the split-K plan): index of TILE_BM / TILE_BN
+    ConvGemm gemm;    // TILES
+    bool strip;       // NARROW: conv_narrow_strip_kernel
+    int cfg;          // streaming kernels: pack_cfg(NT, KC or KS, F)
+    int nsplit, cps;  // the split-K plan of `tile` ((1, 0) without a usable workspace); only TILES launches it
+    int x_bytes;      // streaming kernels: bytes of X (buffer-resource range)
+    bool vec4;        // ConvArgs::vec4
+};
+
+// What route() needs to know about the operands beyond geometry and epilogue: hyres_conv_forward fills it from the
+// real pointers, the host-only queries assume ideal()
+struct ConvFacts {
+    bool xw16;           // x and w2 16-byte aligned, ldx and ldw % 4 == 0
+    bool vec4;           // every epilogue operand 16-byte aligned with ld % 4 == 0, Co % 4 == 0
+    bool rsrc_ok;        // every epilogue operand / output spans < 2 GB
+    bool y8, opnd8;      // y / each of res, aux0, out2 8-byte aligned
+    long long ws_bytes;  // the workspace supplied (0: none)
+    bool ws16;           // ... and 16-byte aligned
+    static ConvFacts ideal() { return {true, true, true, true, true, std::numeric_limits<long long>::max(), true}; }
+};
+
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+static bool fits32(long long bytes) { return bytes < 0x7FFFFFF0LL; }
+
+static int pack_cfg(int nt, int k, int f) { return nt | (k << 4) | (f << 12); }
+static int cfg_nt(int cfg) { return cfg & 15; }
+static int cfg_k(int cfg) { return (cfg >> 4) & 255; }
+static int cfg_f(int cfg) { return cfg >> 12; }
+
 static int g_cus = 0;
 static int num_cus() {
     if (!g_cus) {
@@ -3085,32 +3013,35 @@ static int num_cus() {
     return g_cus;
 }
 
-// blocks per output-channel group: one per CU (persistent), a multiple of 8 so that the group-major block order
-// keeps block bg of every group on XCD bg % 8
-static int wres_blocks(int groups) {
-    return std::max(8, (num_cus() / groups) & ~7);
+static long long gemm_rows(const hyres_conv_geom* g) { return (long long)g->B * g->Hq * g->Wq; }
+
+static int max_taps(const hyres_conv_geom* g) {
+    int maxtap = 0;
+    for (int ph = 0; ph < g->nphase; ++ph) maxtap = std::max(maxtap, g->ntap[ph]);
+    return maxtap;
 }
 
-static bool wres16_ok(const hyres_conv_geom* g) {
-    if (g->Ci != 64) return false;
-    const long long tiles = (long long)g->B * ((g->Ho + HALO_R - 1) / HALO_R) * (g->Wo / HALO_TW);
-    const int groups = g->Co / 64;
-    return tiles >= 2LL * wres_blocks(groups) && (long long)g->B * g->Hi * g->Wi * g->ldx * 4 < 0x7FFFFFF0LL;
+// the epilogue operands are addressed with 32-bit byte offsets (buffer resources)
+static bool epi_span_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
+    const int ld = std::max(g->ldy, std::max(e->res ? e->ldres : 0, e->aux0 ? e->ld0 : 0));
+    return fits32((long long)g->B * g->Ho * g->Wo * ld * 4);
 }
 
-static int launch_wres16(const ConvArgs& a, hipStream_t st) {
-    const hyres_conv_geom& g = a.g;
-    const int ntiles = g.B * ((g.Ho + HALO_R - 1) / HALO_R) * (g.Wo / HALO_TW);
-    const int groups = g.Co / 64;
-    const int per = wres_blocks(groups);
-    const dim3 grid(per * groups);
-    switch (a.e.io_f16 & 3) {
-        case 0: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<0>, grid, dim3(512), 0, st, a, ntiles, groups); break;
-        case 1: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<1>, grid, dim3(512), 0, st, a, ntiles, groups); break;
-        case 2: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<2>, grid, dim3(512), 0, st, a, ntiles, groups); break;
-        default: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<3>, grid, dim3(512), 0, st, a, ntiles, groups); break;
-    }
-    return HY_LAUNCH_CHECK("conv3x3_wres_f16_kernel");
+// single-tap, stride-1, same-size 1x1: the streaming kernels' geometry
+static bool pointwise_same_size(const hyres_conv_geom* g) {
+    return g->nphase == 1 && g->ntaps == 1 && g->ish == 1 && g->isw == 1 && g->dh[0] == 0 && g->dw[0] == 0 &&
+           g->Hi == g->Hq && g->Wi == g->Wq && g->Ho == g->Hq && g->Wo == g->Wq;
+}
+
+// single-phase, stride-1, same-size 3x3 in whole HALO_TW-pixel row tiles: the halo / weight-resident kernels' geometry
+static bool halo_geom(const hyres_conv_geom* g) {
+    return g->nphase == 1 && g->ntaps == 9 && g->ish == 1 && g->isw == 1 && g->Hi == g->Ho && g->Wi == g->Wo &&
+           g->Hq == g->Ho && g->Wq == g->Wo && g->Wo % HALO_TW == 0;
+}
+
+// HALO_R x HALO_TW output tiles of that geometry
+static long long halo_tiles(const hyres_conv_geom* g) {
+    return (long long)g->B * ((g->Ho + HALO_R - 1) / HALO_R) * (g->Wo / HALO_TW);
 }
 
 // the 3x3's largest tap offset (the weight-resident halo radius)
@@ -3120,238 +3051,260 @@ static int wres_halo(const hyres_conv_geom* g) {
     return d;
 }
 
-// conv3x3_wres_f32_kernel: fp32 operands, the halo16 geometry with Ci == 64 and Co % 32 == 0, >= 2 tiles per
-// block
-static bool wres32_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
-    if (g_tune[14] == 0) return false;  // A/B: the implicit GEMM instead
-    if (e->f16_operands || e->io_f16 || e->square_input || e->kind != HYRES_EPI_BIAS || g->nphase != 1 ||
-        g->ntaps != 9 || g->Ci != 64 || g->Co % 32 != 0)
-        return false;
-    // the epilogue operands are addressed with 32-bit byte offsets
-    const long long npix = (long long)g->B * g->Ho * g->Wo;
-    const int ld = std::max(g->ldy, std::max(e->res ? e->ldres : 0, e->aux0 ? e->ld0 : 0));
-    if (npix * ld * 4 >= 0x7FFFFFF0LL) return false;
-    if (g->ish != 1 || g->isw != 1 || g->Hi != g->Ho || g->Wi != g->Wo || g->Hq != g->Ho || g->Wq != g->Wo ||
-        g->Wo % HALO_TW != 0)
-        return false;
-    // halo radius 1, or 2 for the bf16x6 kernel (dilation-2 3x3s: its D = 2 build)
-    if (wres_halo(g) > (g_tune[7] == 1 && g_tune[9] != 0 ? 2 : 1)) return false;
-    const long long tiles = (long long)g->B * ((g->Ho + HALO_R - 1) / HALO_R) * (g->Wo / HALO_TW);
-    const int groups = g->Co / 32;
-    return tiles >= 2LL * wres_blocks(groups) && (long long)g->B * g->Hi * g->Wi * g->ldx * 4 < 0x7FFFFFF0LL;
+// conv3x3_halo_f16_kernel applies (see above)
+static bool halo16_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
+    return e->f16_operands && halo_geom(g) && g->Ci % 32 == 0 && g->Co % 64 == 0 && !e->square_input &&
+           wres_halo(g) <= 1;
 }
+
+// weight-resident 3x3s, blocks per output-channel group: one per CU (persistent), a multiple of 8 so that the
+// group-major block order keeps block bg of every group on XCD bg % 8
+static int wres_blocks(int groups) {
+    return std::max(8, (num_cus() / groups) & ~7);
+}
+
+// ... and their size conditions: enough tiles per block to amortise the one-time weight staging (>= 2 per block),
+// X within a buffer resource
+static bool wres_size_ok(const hyres_conv_geom* g, int groups) {
+    return halo_tiles(g) >= 2LL * wres_blocks(groups) && fits32((long long)g->B * g->Hi * g->Wi * g->ldx * 4);
+}
+
+// conv3x3_wres_f16_kernel: the halo16 geometry with Ci == 64
+static bool wres16_ok(const hyres_conv_geom* g) { return g->Ci == 64 && wres_size_ok(g, g->Co / 64); }
 
 // fp32 GEMM mode of the weight-resident 3x3 (hyres_conv_tuning key 7): 0 = native fp32 MFMA, 1 = bf16x6
 static bool wres_bf6() { return g_tune[7] == 1; }
 
-static int launch_wres32(const ConvArgs& a, hipStream_t st) {
-    const hyres_conv_geom& g = a.g;
-    const int ntiles = g.B * ((g.Ho + HALO_R - 1) / HALO_R) * (g.Wo / HALO_TW);
-    const int groups = g.Co / 32;
-    const int per = wres_blocks(groups);
-    if (wres_bf6()) {
-        const dim3 grid(per * groups);
-        if (wres_halo(&g) == 2)  // dilation 2 (wres32_ok admits it only with the guard on): the pipelined build
-            hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 1, 2>), grid, dim3(512), 0, st, a, ntiles, groups);
-        else if (g_tune[9] == 0)  // diagnostic only: the allocation that let other kernels' waves share its SIMDs
-            hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<false, 0>), grid, dim3(512), 0, st, a, ntiles, groups);
-        else if (g_tune[12] == 1)
-            hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 1>), grid, dim3(512), 0, st, a, ntiles, groups);
-        else if (g_tune[12] == 2)
-            hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 2>), grid, dim3(512), 0, st, a, ntiles, groups);
-        else if (g_tune[12] == 3)
-            hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 3>), grid, dim3(512), 0, st, a, ntiles, groups);
-        else
-            hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 0>), grid, dim3(512), 0, st, a, ntiles, groups);
-        const int rc = HY_LAUNCH_CHECK("conv3x3_wres_bf6_kernel");
-        if (rc || a.e.act != HYRES_ACT_PRELU_MASK) return rc;
-        hipLaunchKernelGGL(prelu_slope_sum_kernel, dim3(1), dim3(256), 0, st, a.e.aux2, (int)grid.x,
-                           const_cast<float*>(a.e.aux1));
-        return HY_LAUNCH_CHECK("prelu_slope_sum_kernel");
+// conv3x3_wres_f32_kernel / conv3x3_wres_bf6_kernel: fp32 operands, the halo16 geometry with Ci == 64 and
+// Co % 32 == 0, >= 2 tiles per block
+static bool wres32_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
+    if (g_tune[14] == 0) return false;  // A/B: the implicit GEMM instead
+    if (e->f16_operands || e->io_f16 || e->square_input || e->kind != HYRES_EPI_BIAS || !halo_geom(g) || g->Ci != 64 ||
+        g->Co % 32 != 0 || !epi_span_ok(g, e))
+        return false;
+    // halo radius 1, or 2 for the bf16x6 kernel (dilation-2 3x3s: its D = 2 build)
+    if (wres_halo(g) > (wres_bf6() && g_tune[9] != 0 ? 2 : 1)) return false;
+    return wres_size_ok(g, g->Co / 32);
+}
+
+// the PReLU-mask epilogues leave one slope-gradient partial per block: summed in a fixed order and added to dst
+static int prelu_slope_sum(const void* partials, int n, const void* dst, hipStream_t st) {
+    hipLaunchKernelGGL(prelu_slope_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, n,
+                       (float*)const_cast<void*>(dst));
+    return HY_LAUNCH_CHECK("prelu_slope_sum_kernel");
+}
+
+static int launch_wres16(const ConvArgs& a, hipStream_t st) {
+    const int ntiles = (int)halo_tiles(&a.g), groups = a.g.Co / 64;
+    const dim3 grid(wres_blocks(groups) * groups);
+    switch (a.e.io_f16 & 3) {
+        case 0: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<0>, grid, dim3(512), 0, st, a, ntiles, groups); break;
+        case 1: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<1>, grid, dim3(512), 0, st, a, ntiles, groups); break;
+        case 2: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<2>, grid, dim3(512), 0, st, a, ntiles, groups); break;
+        default: hipLaunchKernelGGL(conv3x3_wres_f16_kernel<3>, grid, dim3(512), 0, st, a, ntiles, groups); break;
     }
-    hipLaunchKernelGGL(conv3x3_wres_f32_kernel, dim3(per * groups), dim3(512), 0, st, a, ntiles, groups);
-    return HY_LAUNCH_CHECK("conv3x3_wres_f32_kernel");
+    return HY_LAUNCH_CHECK("conv3x3_wres_f16_kernel");
+}
+
+static int launch_wres32(const ConvArgs& a, hipStream_t st) {
+    const int ntiles = (int)halo_tiles(&a.g), groups = a.g.Co / 32;
+    const dim3 grid(wres_blocks(groups) * groups);
+    if (!wres_bf6()) {
+        hipLaunchKernelGGL(conv3x3_wres_f32_kernel, grid, dim3(512), 0, st, a, ntiles, groups);
+        return HY_LAUNCH_CHECK("conv3x3_wres_f32_kernel");
+    }
+    if (wres_halo(&a.g) == 2)  // dilation 2 (wres32_ok admits it only with the guard on): the pipelined build
+        hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 1, 2>), grid, dim3(512), 0, st, a, ntiles, groups);
+    else if (g_tune[9] == 0)  // diagnostic only: the allocation that let other kernels' waves share its SIMDs
+        hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<false, 0>), grid, dim3(512), 0, st, a, ntiles, groups);
+    else if (g_tune[12] == 1)
+        hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 1>), grid, dim3(512), 0, st, a, ntiles, groups);
+    else if (g_tune[12] == 2)
+        hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 2>), grid, dim3(512), 0, st, a, ntiles, groups);
+    else if (g_tune[12] == 3)
+        hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 3>), grid, dim3(512), 0, st, a, ntiles, groups);
+    else
+        hipLaunchKernelGGL((conv3x3_wres_bf6_kernel<true, 0>), grid, dim3(512), 0, st, a, ntiles, groups);
+    const int rc = HY_LAUNCH_CHECK("conv3x3_wres_bf6_kernel");
+    if (rc || a.e.act != HYRES_ACT_PRELU_MASK) return rc;
+    return prelu_slope_sum(a.e.aux2, (int)grid.x, a.e.aux1, st);
 }
 
 static int launch_halo16(const ConvArgs& a, hipStream_t st) {
-    const hyres_conv_geom& g = a.g;
-    const int blocks = g.B * ((g.Ho + HALO_R - 1) / HALO_R) * (g.Wo / HALO_TW) * (g.Co / 64);
+    const dim3 grid((int)halo_tiles(&a.g) * (a.g.Co / 64));
     switch (a.e.io_f16 & 3) {
-        case 0: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<0>, dim3(blocks), dim3(256), 0, st, a); break;
-        case 1: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<1>, dim3(blocks), dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<2>, dim3(blocks), dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<3>, dim3(blocks), dim3(256), 0, st, a); break;
+        case 0: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<0>, grid, dim3(256), 0, st, a); break;
+        case 1: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<1>, grid, dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<2>, grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL(conv3x3_halo_f16_kernel<3>, grid, dim3(256), 0, st, a); break;
     }
     return HY_LAUNCH_CHECK("conv3x3_halo_f16_kernel");
 }
 
-// Kernel choice of hyres_conv_forward, shared with hyres_conv_kernel_name / hyres_conv_plan (the profiler's
-// label). tile: 0 = <2,2,2,2> (128x128), 1 = <2,1,2,2> (128x64), 2 = <1,1,4,1> (128x32), 3 = <1,2,2,2>
-// (64x128), 4 = <1,1,2,2> (64x64).
-//   * short-K 1x1 layers (<= 4 K chunks): half-height tiles — the short main loop cannot hide the operand
-//     and epilogue latencies, so twice as many blocks go in flight;
-//   * small grids (<= 65536 output pixels: the 64^2 and 32^2 regions at bs 16): 64-row tiles, 64 wide up to
-//     192 channels (fp32) / below 192 (f16), else 64x128 (fp32) / 128x128 (f16); measured per geometry
-//     over every tile and split-K target (scripts/tile_sweep.py, profiles/r2_tile_sweep_*.txt);
-//   * the scalar-load path (Ci % 32 != 0: the 3-channel image side) 64-row tiles (3->64 at 256^2: 198 -> 140 us);
-//   * otherwise 128-row tiles as wide as Co allows.
-// Split-K engages only when the chosen tile leaves fewer than 512 blocks and K has >= 8 chunks.
-struct ConvChoice {
-    bool narrow;
-    int tile, mode;
-};
+// the streamed epilogue operands as the streaming kernels' F bits: residual, ReLU mask, old y
+static int stream_f(const hyres_epilogue* e) {
+    return (e->res ? 1 : 0) | (e->act == HYRES_ACT_RELU_MASK ? 2 : 0) | (e->accumulate ? 4 : 0);
+}
+
 // conv1x1_stream_kernel eligibility: single-tap stride-1 fp32 1x1 with K = Ci in {64, 96, 128}, Co in
 // {64, 96, 128} (or 192 with K = 64), BIAS epilogue with no streamed operand (residual / ReLU mask /
-// old y), grids >= 65536 output pixels. Returns NT (Co / 32) or 0.
-static int stream_nt(const hyres_conv_geom* g, const hyres_epilogue* e) {
-    constexpr long long min_px = 65536;
+// old y), grids >= 65536 output pixels. Returns pack_cfg(NT = Co / 32, KC = Ci / 8, 0) or 0.
+static int stream_cfg(const hyres_conv_geom* g, const hyres_epilogue* e) {
     if ((e->io_f16 & 3) || e->square_input || e->kind != HYRES_EPI_BIAS) return 0;
-    if (g->nphase != 1 || g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0) return 0;
-    if (g->Hi != g->Hq || g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq) return 0;
-    if ((long long)g->B * g->Hq * g->Wq < min_px) return 0;
+    if (!pointwise_same_size(g) || gemm_rows(g) < 65536) return 0;
     if (g->Ci != 64 && g->Ci != 96 && g->Ci != 128) return 0;
-    if (e->res || e->act == HYRES_ACT_RELU_MASK || e->accumulate) return 0;
-    if (g->Co == 64 || g->Co == 96 || g->Co == 128) return g->Co / 32;
-    if (g->Co == 192 && g->Ci == 64) return 6;
-    return 0;
+    if (stream_f(e)) return 0;
+    const bool co = g->Co == 64 || g->Co == 96 || g->Co == 128 || (g->Co == 192 && g->Ci == 64);
+    return co ? pack_cfg(g->Co / 32, g->Ci / 8, 0) : 0;
 }
 
 // conv1x1_stream_h_kernel eligibility: fp16 X and Y (io_f16 = 3), single-tap stride-1 1x1 with Ci and Co in
 // {64, 96, 128}, BIAS epilogue with ReLU / none and no streamed operand, grids >= 16384 output pixels, 16-byte X rows.
-// Returns NT (Co / 32) or 0.
-static int stream_h_nt(const hyres_conv_geom* g, const hyres_epilogue* e) {
+// Returns pack_cfg(NT = Co / 32, KC = Ci / 16, 0) or 0.
+static int stream_h_cfg(const hyres_conv_geom* g, const hyres_epilogue* e) {
     if (g_tune[8] == 0 || (e->io_f16 & 3) != 3 || e->square_input || e->kind != HYRES_EPI_BIAS || e->out2) return 0;
     // a streamed epilogue operand (residual, ReLU mask, old y) measured slower than the tiles (128^2 64->128 +res
     // 45.2 vs 43.5 us, 64^2 16.5 vs 13.9 us; without one 24.8 vs 30.7 and 60.3 vs 80.8 us: profiles/r4e_h1x1.txt),
     // as for the fp32 streaming kernel: those layers stay tiled
-    if (e->res || e->act == HYRES_ACT_RELU_MASK || e->accumulate) return 0;
+    if (stream_f(e)) return 0;
     if (e->act != HYRES_ACT_NONE && e->act != HYRES_ACT_RELU) return 0;
-    if (g->nphase != 1 || g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0) return 0;
-    if (g->Hi != g->Hq || g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq) return 0;
-    if ((long long)g->B * g->Hq * g->Wq < 16384) return 0;
+    if (!pointwise_same_size(g) || gemm_rows(g) < 16384) return 0;
     if (g->Ci != 64 && g->Ci != 96 && g->Ci != 128) return 0;
     if (g->Co != 64 && g->Co != 96 && g->Co != 128) return 0;
     if (g->ldx % 8 || g->ldy % 4) return 0;
-    return g->Co / 32;
+    return pack_cfg(g->Co / 32, g->Ci / 16, 0);
+}
+
+// the fusion 1x1's input-gradient 64 -> 192 (HYRES_EPI_SA_BWD, round 6) as conv1x1_stream_b6_kernel /
+// conv1x1_stream_hf_kernel run it: plain, accumulating, or with the scale-1 PReLU backward (pm). Returns their F, or 0.
+static int sa_bwd_f(const hyres_conv_geom* g, const hyres_epilogue* e) {
+    const bool pm = e->act == HYRES_ACT_PRELU_MASK && !e->accumulate;
+    if (g_tune[21] == 0 || g->Ci != 64 || g->Co != 192 || (e->act != HYRES_ACT_NONE && !pm) || (e->res && !pm) ||
+        (e->out2 && !pm) || (pm && (!e->aux1 || e->ld1 < 64 || e->ld1 % 4 || !e->res)))
+        return 0;
+    return pm ? 40 : (8 | (e->accumulate ? 4 : 0));
+}
+
+// the fusion 1x1 forward 192 -> 64 with SpatialAttention folded (HYRES_EPI_ROWSCALE, round 6) on the same two kernels
+static bool rowscale_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
+    return g_tune[21] != 0 && g->Ci == 192 && g->Co == 64 && !e->res && !e->accumulate &&
+           (e->act == HYRES_ACT_NONE || e->act == HYRES_ACT_RELU || e->act == HYRES_ACT_PRELU);
 }
 
 // conv1x1_stream_hf_kernel eligibility (hyres_conv_tuning key 17 = 1, default): fp16 X and Y / operands (io_f16 = 3),
 // f16 operands, single-tap stride-1 1x1, (Ci, Co) in {64, 128}^2, >= 16384 output pixels, BIAS epilogue with none /
 // ReLU / ReLU mask and at least one streamed operand (residual, mask, old y; without one: conv1x1_stream_h_kernel),
-// no out2, 16-byte X rows / 8-byte Y rows. Returns NT | KC << 4 | F << 8, or 0.
+// no out2, 16-byte X rows / 8-byte Y rows. Returns pack_cfg(NT, KC, F), or 0.
 static int stream_hf_cfg(const hyres_conv_geom* g, const hyres_epilogue* e) {
     if (g_tune[17] == 0 || (e->io_f16 & 3) != 3 || !e->f16_operands || e->square_input) return 0;
-    if (e->kind == HYRES_EPI_ROWSCALE) {  // round 6: the fusion 1x1 forward under AMP with SpatialAttention folded
-        if (g_tune[21] == 0 || g->Ci != 192 || g->Co != 64 || e->res || e->accumulate || !e->out2 || e->ldo2 % 4 ||
-            (e->act != HYRES_ACT_NONE && e->act != HYRES_ACT_RELU && e->act != HYRES_ACT_PRELU) || g->nphase != 1 ||
-            g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0 || g->Hi != g->Hq ||
-            g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq || (long long)g->B * g->Hq * g->Wq < 16384 ||
-            g->ldx % 8 || g->ldy % 4)
-            return 0;
-        return 2 | (12 << 4) | (16 << 8);
+    if (!pointwise_same_size(g) || gemm_rows(g) < 16384 || g->ldx % 8 || g->ldy % 4) return 0;
+    if (e->kind == HYRES_EPI_ROWSCALE)  // the fusion 1x1 forward under AMP
+        return rowscale_ok(g, e) && e->out2 && e->ldo2 % 4 == 0 ? pack_cfg(2, 12, 16) : 0;
+    if (e->kind == HYRES_EPI_SA_BWD) {  // the fusion 1x1's input-gradient under AMP
+        const int F = e->ld0 % 2 ? 0 : sa_bwd_f(g, e);
+        return F ? pack_cfg(6, 4, F) : 0;
     }
-    if (e->kind == HYRES_EPI_SA_BWD) {  // round 6: the fusion 1x1's input-gradient under AMP, 64 -> 192
-        const bool pm = e->act == HYRES_ACT_PRELU_MASK && !e->accumulate;  // + the scale-1 PReLU backward
-        if (g_tune[21] == 0 || g->Ci != 64 || g->Co != 192 || (e->act != HYRES_ACT_NONE && !pm) || (e->res && !pm) ||
-            (e->out2 && !pm) || (pm && (!e->aux1 || e->ld1 < 64 || e->ld1 % 4 || !e->res)) || g->nphase != 1 ||
-            g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0 || g->Hi != g->Hq ||
-            g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq || (long long)g->B * g->Hq * g->Wq < 16384 ||
-            g->ldx % 8 || g->ldy % 4 || e->ld0 % 2)
-            return 0;
-        return 6 | (4 << 4) | ((pm ? 40 : (8 | (e->accumulate ? 4 : 0))) << 8);
-    }
-    if (e->out2) return 0;
-    if (e->kind != HYRES_EPI_BIAS) return 0;
+    if (e->out2 || e->kind != HYRES_EPI_BIAS) return 0;
     if (e->act != HYRES_ACT_NONE && e->act != HYRES_ACT_RELU && e->act != HYRES_ACT_RELU_MASK) return 0;
-    if (g->nphase != 1 || g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0) return 0;
-    if (g->Hi != g->Hq || g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq) return 0;
-    if ((long long)g->B * g->Hq * g->Wq < 16384) return 0;
     if ((g->Ci != 64 && g->Ci != 128) || (g->Co != 64 && g->Co != 128)) return 0;
-    if (g->ldx % 8 || g->ldy % 4 || (e->res && e->ldres % 4) || (e->act == HYRES_ACT_RELU_MASK && e->ld0 % 4)) return 0;
-    const int F = (e->res ? 1 : 0) | (e->act == HYRES_ACT_RELU_MASK ? 2 : 0) | (e->accumulate ? 4 : 0);
-    if (!F) return 0;
-    return (g->Co / 32) | ((g->Ci / 16) << 4) | (F << 8);
+    if ((e->res && e->ldres % 4) || (e->act == HYRES_ACT_RELU_MASK && e->ld0 % 4)) return 0;
+    const int F = stream_f(e);
+    return F ? pack_cfg(g->Co / 32, g->Ci / 16, F) : 0;
 }
+
+// conv1x1_stream_b6_kernel's epilogue: coalesced (hyres_conv_tuning key 11, default) or per-fragment stores
+static bool stream_b6_ce() { return g_tune[11] != 0; }
 
 // conv1x1_stream_b6_kernel eligibility (bf16x6 fp32 GEMMs, hyres_conv_tuning key 10 = 1): fp32 X / Y, single-tap
 // stride-1 1x1 with (Ci, Co) in {(64, 64), (64, 128), (128, 64)}, BIAS epilogue with none / ReLU / PReLU / ReLU mask,
-// any of residual / mask / accumulate, grids >= 65536 output pixels. Returns the packed choice NT | KS << 4 | F << 8,
-// or 0.
+// any of residual / mask / accumulate, grids >= 65536 output pixels. Returns pack_cfg(NT, KS, F), or 0.
 static int stream_b6_cfg(const hyres_conv_geom* g, const hyres_epilogue* e) {
     if (g_tune[7] != 1 || g_tune[10] == 0) return 0;
     if (e->io_f16 || e->f16_operands || e->square_input) return 0;
-    if (e->kind == HYRES_EPI_SA_BWD) {  // round 6: the fusion 1x1's input-gradient, 64 -> 192 (coalesced epilogue only)
-        const bool pm = e->act == HYRES_ACT_PRELU_MASK && !e->accumulate;
-        if (g_tune[11] == 0 || g_tune[21] == 0 || g->Ci != 64 || g->Co != 192 || (e->act != HYRES_ACT_NONE && !pm) ||
-            (e->res && !pm) || (e->out2 && !pm) || (pm && (!e->aux1 || e->ld1 < 64 || e->ld1 % 4 || !e->res)) ||
-            g->nphase != 1 || g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0 ||
-            g->Hi != g->Hq || g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq || (long long)g->B * g->Hq * g->Wq < 65536)
-            return 0;
-        return 6 | (4 << 4) | ((pm ? 40 : (8 | (e->accumulate ? 4 : 0))) << 8);
+    if (!pointwise_same_size(g) || gemm_rows(g) < 65536) return 0;
+    if (e->kind == HYRES_EPI_SA_BWD) {  // the fusion 1x1's input-gradient (coalesced epilogue only)
+        const int F = stream_b6_ce() ? sa_bwd_f(g, e) : 0;
+        return F ? pack_cfg(6, 4, F) : 0;
     }
-    if (g->nphase != 1 || g->ntaps != 1 || g->ish != 1 || g->isw != 1 || g->dh[0] != 0 || g->dw[0] != 0) return 0;
-    if (g->Hi != g->Hq || g->Wi != g->Wq || g->Ho != g->Hq || g->Wo != g->Wq) return 0;
-    if ((long long)g->B * g->Hq * g->Wq < 65536) return 0;
-    if (e->kind == HYRES_EPI_ROWSCALE) {  // round 6: the fusion 1x1 forward with SpatialAttention folded, 192 -> 64
-        if (g_tune[11] == 0 || g_tune[21] == 0 || g->Ci != 192 || g->Co != 64 || e->res || e->accumulate ||
-            (e->act != HYRES_ACT_NONE && e->act != HYRES_ACT_RELU && e->act != HYRES_ACT_PRELU))
-            return 0;
-        return 2 | (12 << 4) | (16 << 8);
-    }
+    if (e->kind == HYRES_EPI_ROWSCALE)  // the fusion 1x1 forward (coalesced epilogue only)
+        return stream_b6_ce() && rowscale_ok(g, e) ? pack_cfg(2, 12, 16) : 0;
     if (e->kind != HYRES_EPI_BIAS) return 0;
     const bool shape = (g->Ci == 64 && (g->Co == 64 || g->Co == 128)) || (g->Ci == 128 && g->Co == 64) ||
                        (g->Ci == 128 && g->Co == 128);
     if (!shape) return 0;
-    const int F = (e->res ? 1 : 0) | (e->act == HYRES_ACT_RELU_MASK ? 2 : 0) | (e->accumulate ? 4 : 0);
+    const int F = stream_f(e);
     // 128 -> 128 (round 6, the GDN-side 1x1s at 128^2): 122 KB of LDS, one wave per SIMD — built for the operand-free
     // and ReLU-mask forms only
     if (g->Ci == 128 && g->Co == 128 && F != 0 && F != 2) return 0;
-    return (g->Co / 32) | ((g->Ci / 16) << 4) | (F << 8);
+    return pack_cfg(g->Co / 32, g->Ci / 16, F);
 }
 
-extern "C++" {
-template <int NT, int KC>
-static int launch_stream_h_one(const ConvArgs& a, hipStream_t st) {
+// persistent grid of a streaming kernel: as many blocks as fit on the chip at once (occupancy query, cached per
+// instantiation), capped by the 32-pixel tiles available (4 per block)
+template <auto Kernel>
+static int persistent_blocks(int M) {
     static int occ = -1;
     if (occ < 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv1x1_stream_h_kernel<NT, KC>, 256, 0) != hipSuccess ||
-            n < 1)
-            n = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, 256, 0) != hipSuccess || n < 1) n = 1;
         occ = n;
     }
-    const int blocks = std::max(1, std::min(ceil_div(ceil_div(a.M, 32), 4), 256 * occ));
-    hipLaunchKernelGGL((conv1x1_stream_h_kernel<NT, KC>), dim3(blocks), dim3(256), 0, st, a);
-    return HY_LAUNCH_CHECK("conv1x1_stream_h_kernel");
+    return std::max(1, std::min(ceil_div(ceil_div(M, 32), 4), num_cus() * occ));
 }
-}  // extern "C++"
 
-extern "C++" {
+// ... launched; with F & 32 (the PReLU mask) every block leaves a slope partial in out2[blockIdx.x]
+template <auto Kernel, int F>
+static int launch_persistent(const ConvArgs& a, const char* name, hipStream_t st) {
+    const int blocks = persistent_blocks<Kernel>(a.M);
+    if constexpr ((F & 32) != 0)
+        HY_REQUIRE(blocks <= a.e.ldo2, HYRES_E_ARG, "%s: %d blocks, out2 holds %d slope partials", name, blocks,
+                   a.e.ldo2);
+    hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(256), 0, st, a);
+    const int rc = HY_LAUNCH_CHECK(name);
+    if constexpr ((F & 32) != 0) return rc ? rc : prelu_slope_sum(a.e.out2, blocks, a.e.res, st);
+    return rc;
+}
+
+template <int NT, int KC>
+static int launch_stream_one(const ConvArgs& a, hipStream_t st) {
+    // (the f16-operand build runs on the fp32 build's block count)
+    const dim3 grid(persistent_blocks<conv1x1_stream_kernel<NT, KC>>(a.M));
+    if (a.e.f16_operands) hipLaunchKernelGGL((conv1x1_stream_kernel<NT, KC, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv1x1_stream_kernel<NT, KC>), grid, dim3(256), 0, st, a);
+    return HY_LAUNCH_CHECK("conv1x1_stream_kernel");
+}
+
+static int launch_stream(const ConvArgs& a, int cfg, hipStream_t st) {
+    const int nt = cfg_nt(cfg), kc = cfg_k(cfg);
+#define HY_STREAM(NT, KC) \
+    if (nt == NT && kc == KC) return launch_stream_one<NT, KC>(a, st);
+    HY_STREAM(2, 8) HY_STREAM(2, 12) HY_STREAM(2, 16)
+    HY_STREAM(3, 8) HY_STREAM(3, 12) HY_STREAM(3, 16)
+    HY_STREAM(4, 8) HY_STREAM(4, 12) HY_STREAM(4, 16)
+    HY_STREAM(6, 8)
+#undef HY_STREAM
+    return set_error(HYRES_E_ARG, "conv1x1_stream: no instantiation for NT=%d KC=%d", nt, kc);
+}
+
+static int launch_stream_h(const ConvArgs& a, int cfg, hipStream_t st) {
+    const int nt = cfg_nt(cfg), kc = cfg_k(cfg);
+#define HY_STREAM_H(NT, KC) \
+    if (nt == NT && kc == KC) \
+        return launch_persistent<conv1x1_stream_h_kernel<NT, KC>, 0>(a, "conv1x1_stream_h_kernel", st);
+    HY_STREAM_H(2, 4) HY_STREAM_H(2, 6) HY_STREAM_H(2, 8)
+    HY_STREAM_H(3, 4) HY_STREAM_H(3, 6) HY_STREAM_H(3, 8)
+    HY_STREAM_H(4, 4) HY_STREAM_H(4, 6) HY_STREAM_H(4, 8)
+#undef HY_STREAM_H
+    return set_error(HYRES_E_ARG, "conv1x1_stream_h: no instantiation for NT=%d KC=%d", nt, kc);
+}
+
 template <int NT, int KS, int F, bool CE>
 static int launch_stream_b6_ce(const ConvArgs& a, hipStream_t st) {
-    static int occ = -1;
-    if (occ < 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv1x1_stream_b6_kernel<NT, KS, F, CE>, 256, 0) !=
-                hipSuccess ||
-            n < 1)
-            n = 1;
-        occ = n;
-    }
-    const int blocks = std::max(1, std::min(ceil_div(ceil_div(a.M, 32), 4), num_cus() * occ));
-    hipLaunchKernelGGL((conv1x1_stream_b6_kernel<NT, KS, F, CE>), dim3(blocks), dim3(256), 0, st, a);
-    if constexpr ((F & 32) != 0) {  // the PReLU mask's slope partials, summed in a fixed order and added
-        const int rc = HY_LAUNCH_CHECK("conv1x1_stream_b6_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL(prelu_slope_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)a.e.out2, blocks,
-                           const_cast<float*>(a.e.res));
-        return HY_LAUNCH_CHECK("prelu_slope_sum_kernel");
-    }
-    return HY_LAUNCH_CHECK("conv1x1_stream_b6_kernel");
+    return launch_persistent<conv1x1_stream_b6_kernel<NT, KS, F, CE>, F>(a, "conv1x1_stream_b6_kernel", st);
 }
 template <int NT, int KS, int F>
 static int launch_stream_b6_one(const ConvArgs& a, hipStream_t st) {
-    return g_tune[11] == 0 ? launch_stream_b6_ce<NT, KS, F, false>(a, st) : launch_stream_b6_ce<NT, KS, F, true>(a, st);
+    return stream_b6_ce() ? launch_stream_b6_ce<NT, KS, F, true>(a, st) : launch_stream_b6_ce<NT, KS, F, false>(a, st);
 }
 template <int NT, int KS>
 static int launch_stream_b6_f(const ConvArgs& a, int f, hipStream_t st) {
@@ -3366,10 +3319,9 @@ static int launch_stream_b6_f(const ConvArgs& a, int f, hipStream_t st) {
         default: return launch_stream_b6_one<NT, KS, 7>(a, st);
     }
 }
-}  // extern "C++"
 
 static int launch_stream_b6(const ConvArgs& a, int cfg, hipStream_t st) {
-    const int nt = cfg & 15, ks = (cfg >> 4) & 15, f = cfg >> 8;
+    const int nt = cfg_nt(cfg), ks = cfg_k(cfg), f = cfg_f(cfg);
     if (nt == 6 && ks == 4 && f == 8) return launch_stream_b6_ce<6, 4, 8, true>(a, st);
     if (nt == 6 && ks == 4 && f == 12) return launch_stream_b6_ce<6, 4, 12, true>(a, st);
     if (nt == 6 && ks == 4 && f == 40) return launch_stream_b6_ce<6, 4, 40, true>(a, st);
@@ -3382,27 +3334,9 @@ static int launch_stream_b6(const ConvArgs& a, int cfg, hipStream_t st) {
     return set_error(HYRES_E_ARG, "conv1x1_stream_b6: no instantiation for NT=%d KS=%d", nt, ks);
 }
 
-extern "C++" {
 template <int NT, int KC, int F>
 static int launch_stream_hf_one(const ConvArgs& a, hipStream_t st) {
-    static int occ = -1;
-    if (occ < 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv1x1_stream_hf_kernel<NT, KC, F>, 256, 0) != hipSuccess ||
-            n < 1)
-            n = 1;
-        occ = n;
-    }
-    const int blocks = std::max(1, std::min(ceil_div(ceil_div(a.M, 32), 4), num_cus() * occ));
-    hipLaunchKernelGGL((conv1x1_stream_hf_kernel<NT, KC, F>), dim3(blocks), dim3(256), 0, st, a);
-    if constexpr ((F & 32) != 0) {  // the PReLU mask's slope partials, summed in a fixed order and added
-        const int rc = HY_LAUNCH_CHECK("conv1x1_stream_hf_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL(prelu_slope_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)a.e.out2, blocks,
-                           const_cast<float*>(a.e.res));
-        return HY_LAUNCH_CHECK("prelu_slope_sum_kernel");
-    }
-    return HY_LAUNCH_CHECK("conv1x1_stream_hf_kernel");
+    return launch_persistent<conv1x1_stream_hf_kernel<NT, KC, F>, F>(a, "conv1x1_stream_hf_kernel", st);
 }
 template <int NT, int KC>
 static int launch_stream_hf_f(const ConvArgs& a, int f, hipStream_t st) {
@@ -3416,10 +3350,9 @@ static int launch_stream_hf_f(const ConvArgs& a, int f, hipStream_t st) {
         default: return launch_stream_hf_one<NT, KC, 7>(a, st);
     }
 }
-}  // extern "C++"
 
 static int launch_stream_hf(const ConvArgs& a, int cfg, hipStream_t st) {
-    const int nt = cfg & 15, kc = (cfg >> 4) & 15, f = cfg >> 8;
+    const int nt = cfg_nt(cfg), kc = cfg_k(cfg), f = cfg_f(cfg);
     if (nt == 6 && kc == 4 && f == 8) return launch_stream_hf_one<6, 4, 8>(a, st);
     if (nt == 6 && kc == 4 && f == 12) return launch_stream_hf_one<6, 4, 12>(a, st);
     if (nt == 6 && kc == 4 && f == 40) return launch_stream_hf_one<6, 4, 40>(a, st);
@@ -3431,26 +3364,20 @@ static int launch_stream_hf(const ConvArgs& a, int cfg, hipStream_t st) {
     return set_error(HYRES_E_ARG, "conv1x1_stream_hf: no instantiation for NT=%d KC=%d", nt, kc);
 }
 
-static int launch_stream_h(const ConvArgs& a, int nt, int kc, hipStream_t st) {
-#define HY_STREAM_H(NT, KC) \
-    if (nt == NT && kc == KC) return launch_stream_h_one<NT, KC>(a, st);
-    HY_STREAM_H(2, 4) HY_STREAM_H(2, 6) HY_STREAM_H(2, 8)
-    HY_STREAM_H(3, 4) HY_STREAM_H(3, 6) HY_STREAM_H(3, 8)
-    HY_STREAM_H(4, 4) HY_STREAM_H(4, 6) HY_STREAM_H(4, 8)
-#undef HY_STREAM_H
-    return set_error(HYRES_E_ARG, "conv1x1_stream_h: no instantiation for NT=%d KC=%d", nt, kc);
-}
-
 static const int TILE_BM[5] = {128, 128, 128, 64, 64};
 static const int TILE_BN[5] = {128, 64, 32, 128, 64};
 
-// Tile / split-K overrides set through hyres_conv_tuning (tuning sweeps; -1 = the heuristics below)
-// keys: HYRES_TUNE_TILE, _SPLIT_BLOCKS, _SPLIT_MINCHUNKS, _WGRAD_BLOCKS, _WGRAD_MINCHUNKS, _WGRAD_NT
-
-static ConvChoice choose_conv(const hyres_conv_geom* g, const hyres_epilogue* e, bool aligned) {
-    ConvChoice c{};
-    c.mode = (g->Ci % KT == 0) ? (e->square_input ? 1 : 0) : 2;
-    c.narrow = narrow_ok(g) && !e->square_input && e->kind == HYRES_EPI_BIAS && aligned;
+// Tile of the implicit GEMM. tile: 0 = <2,2,2,2> (128x128), 1 = <2,1,2,2> (128x64), 2 = <1,1,4,1> (128x32),
+// 3 = <1,2,2,2> (64x128), 4 = <1,1,2,2> (64x64).
+//   * short-K 1x1 layers (<= 4 K chunks): half-height tiles — the short main loop cannot hide the operand
+//     and epilogue latencies, so twice as many blocks go in flight;
+//   * small grids (<= 65536 output pixels: the 64^2 and 32^2 regions at bs 16): 64-row tiles, 64 wide up to
+//     192 channels (fp32) / below 192 (f16), else 64x128 (fp32) / 128x128 (f16); measured per geometry
+//     over every tile and split-K target (scripts/tile_sweep.py, profiles/r2_tile_sweep_*.txt);
+//   * the scalar-load path (Ci % 32 != 0: the 3-channel image side) 64-row tiles (3->64 at 256^2: 198 -> 140 us);
+//   * otherwise 128-row tiles as wide as Co allows.
+// hyres_conv_tuning key HYRES_TUNE_TILE overrides it (tuning sweeps; -1 = these heuristics).
+static void choose_tile(const hyres_conv_geom* g, const hyres_epilogue* e, ConvRoute& c) {
     constexpr long long small_px = 65536;
     const bool f16 = e->f16_operands && c.mode != 2;
     const bool short_k = c.mode != 2 && g->nphase == 1 && g->ntaps == 1 && g->Ci <= 4 * KT;
@@ -3478,38 +3405,180 @@ static ConvChoice choose_conv(const hyres_conv_geom* g, const hyres_epilogue* e,
     else if (g->Co > 32) c.tile = 1;
     else c.tile = 2;
     if (g_tune[0] >= 0 && g_tune[0] <= 4) c.tile = g_tune[0];
-    return c;
 }
 
-struct ConvPlan {
-    int nsplit, cps;
-};
-
-static ConvPlan conv_plan(const hyres_conv_geom* g, int tile) {
-    ConvPlan p{};
-    const long long M = (long long)g->B * g->Hq * g->Wq;
-    long long blocks = (long long)ceil_div(M, TILE_BM[tile]) * ceil_div(g->Co, TILE_BN[tile]) * g->nphase;
-    int maxtap = 0;
-    for (int ph = 0; ph < g->nphase; ++ph) maxtap = std::max(maxtap, g->ntap[ph]);
+// Split-K of the implicit GEMM on r.tile: engages only when the tile leaves fewer than 512 blocks and K has >= 8
+// chunks (keys HYRES_TUNE_SPLIT_BLOCKS, _SPLIT_MINCHUNKS)
+static void plan_split(const hyres_conv_geom* g, ConvRoute& r) {
+    const long long blocks =
+        (long long)ceil_div(gemm_rows(g), TILE_BM[r.tile]) * ceil_div(g->Co, TILE_BN[r.tile]) * g->nphase;
+    const int maxtap = max_taps(g);
     const int nk = (g->Ci % KT == 0) ? maxtap * (g->Ci / KT) : ceil_div((long long)maxtap * g->Ci, KT);
-    p.nsplit = 1;
-    p.cps = nk;
+    r.nsplit = 1;
+    r.cps = nk;
     const int sb = g_tune[1] >= 0 ? g_tune[1] : 512;
     const int sc = g_tune[2] > 0 ? g_tune[2] : 4;
     if (blocks < sb && nk >= 2 * sc) {
         // split K so that ~sb blocks are in flight, at least sc chunks per split
         int want = (int)std::min<long long>(ceil_div(sb, blocks), 64);
         int ns = std::max(1, std::min(want, nk / sc));
-        p.cps = ceil_div(nk, ns);
-        p.nsplit = ceil_div(nk, p.cps);
+        r.cps = ceil_div(nk, ns);
+        r.nsplit = ceil_div(nk, r.cps);
     }
-    return p;
 }
 
-static long long plan_ws_bytes(const hyres_conv_geom* g, const ConvPlan& p) {
-    if (p.nsplit <= 1) return 0;
-    return (long long)p.nsplit * g->nphase * ((long long)g->B * g->Hq * g->Wq) * g->Co * 4;
+static long long split_ws_bytes(const hyres_conv_geom* g, int nsplit) {
+    if (nsplit <= 1) return 0;
+    return (long long)nsplit * g->nphase * gemm_rows(g) * g->Co * 4;
 }
+
+static ConvGemm choose_gemm(const hyres_conv_geom* g, const hyres_epilogue* e, const ConvRoute& r) {
+    if (e->io_f16 & 3) return ConvGemm::H;
+    if (r.mode == 2) return ConvGemm::F32;
+    if (e->f16_operands) return ConvGemm::F16;
+    if (g_tune[7] != 1) return ConvGemm::F32;  // fp32 GEMM on the fp32 MFMA; else on the bf16 MFMA (bf16x6)
+    // double-buffered staging (key 20 = 1, or -1: on for the <= 16384-pixel grids). Isolated it wins at 32^2
+    // (3x3 96 -> 96 39.6 -> 37.3 us, 1x1 192 -> 96 13.9 -> 13.1 us) and loses on the larger-K 64^2 / 5x5 layers
+    // (+2..5 %: the 49 KB of LDS cost the 4th block per CU, profiles/r6m_b6db.txt); in the graphed step the
+    // small-grid rule measured 0.2-0.3 ms SLOWER (profiles/r6n_b6db_step_ab.txt: those layers run beside the
+    // branch streams' kernels), so the default is off
+    const bool db = r.tile == 4 && (g_tune[20] == 1 || (g_tune[20] < 0 && gemm_rows(g) <= 16384));
+    return db ? ConvGemm::B6DB : ConvGemm::B6;
+}
+
+// The one kernel choice, in this order: narrow, weight-resident fp32 3x3, halo / weight-resident f16 3x3, the four
+// streaming 1x1s (bf16x6, fp32, f16 with a streamed operand, f16 without), the implicit-GEMM tiles.
+static ConvRoute route(const hyres_conv_geom* g, const hyres_epilogue* e, const ConvFacts& f) {
+    ConvRoute r{};
+    r.mode = (g->Ci % KT == 0) ? (e->square_input ? 1 : 0) : 2;
+    choose_tile(g, e, r);
+    r.nsplit = 1;
+    r.vec4 = f.vec4;
+    if (narrow_ok(g) && !e->square_input && e->kind == HYRES_EPI_BIAS && f.xw16) {
+        r.family = ConvFamily::NARROW;
+        r.strip = narrow_strip_ok(g);
+        return r;
+    }
+    plan_split(g, r);
+    if (r.nsplit > 1 && f.ws_bytes >= split_ws_bytes(g, r.nsplit)) {
+        r.vec4 = f.vec4 && f.ws16;  // the slab is read four floats at a time
+    } else {  // without workspace: single pass (correct, slower)
+        r.nsplit = 1;
+        r.cps = 0;
+    }
+    const bool vec = r.mode == 0 && f.xw16;
+    if (vec && r.vec4 && wres32_ok(g, e)) {
+        r.family = ConvFamily::WRES32;
+        return r;
+    }
+    if (vec && r.vec4 && halo16_ok(g, e)) {
+        r.family = wres16_ok(g) ? ConvFamily::WRES16 : ConvFamily::HALO16;
+        return r;
+    }
+    // a streaming kernel takes the layer if it is eligible (cfg != 0) and X fits a buffer resource
+    auto stream = [&](ConvFamily family, int cfg, int x_elem) {
+        const long long xb = gemm_rows(g) * g->ldx * x_elem;
+        if (!cfg || !fits32(xb)) return false;
+        r.family = family;
+        r.cfg = cfg;
+        r.x_bytes = (int)xb;
+        return true;
+    };
+    if (vec && r.vec4 && f.rsrc_ok && stream(ConvFamily::STREAM_B6, stream_b6_cfg(g, e), 4)) return r;
+    if (vec && r.vec4 && stream(ConvFamily::STREAM, stream_cfg(g, e), 4)) return r;
+    if (vec && f.rsrc_ok && f.y8 && f.opnd8 && stream(ConvFamily::STREAM_HF, stream_hf_cfg(g, e), 2)) return r;
+    if (vec && f.y8 && stream(ConvFamily::STREAM_H, stream_h_cfg(g, e), 2)) return r;
+    r.family = ConvFamily::TILES;
+    r.gemm = choose_gemm(g, e, r);
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------------
+static int launch_narrow_co(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    const dim3 grid(ceil_div(a.M, NARROW_PIX), a.g.nphase);
+    switch (a.g.Co) {
+        case 1: launch_narrow<1>(a, r.strip, grid, st); break;
+        case 2: launch_narrow<2>(a, r.strip, grid, st); break;
+        case 3: launch_narrow<3>(a, r.strip, grid, st); break;
+        default: launch_narrow<4>(a, r.strip, grid, st); break;
+    }
+    return HY_LAUNCH_CHECK("conv_narrow_kernel");
+}
+
+// the implicit GEMM on one tile; split-K launches are a separate instantiation (partials to the slab, no epilogue)
+template <int TM, int TN, int WM_, int WN_>
+static int launch_fwd(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    constexpr int BM = 32 * TM * WM_, BN = 32 * TN * WN_;
+    dim3 grid(ceil_div(a.M, BM), ceil_div(a.g.Co, BN), a.g.nphase * a.nsplit);
+    if (a.xcd) grid = dim3(grid.x * grid.y, 1, grid.z);
+    // KERNEL<tile, MODE_, split, trailing template arguments>
+#define HY_TILES(KERNEL, MODE_, ...)                                                                                   \
+    do {                                                                                                               \
+        if (a.nsplit > 1)                                                                                              \
+            hipLaunchKernelGGL((KERNEL<TM, TN, WM_, WN_, MODE_, true __VA_ARGS__>), grid, dim3(256), 0, st, a);        \
+        else                                                                                                           \
+            hipLaunchKernelGGL((KERNEL<TM, TN, WM_, WN_, MODE_, false __VA_ARGS__>), grid, dim3(256), 0, st, a);       \
+    } while (0)
+#define HY_TILES_01(KERNEL, ...)                              \
+    do {                                                      \
+        if (r.mode == 0) HY_TILES(KERNEL, 0, __VA_ARGS__);    \
+        else HY_TILES(KERNEL, 1, __VA_ARGS__);                \
+    } while (0)
+    switch (r.gemm) {
+        case ConvGemm::H:
+            if (r.mode == 2) HY_TILES(conv_fwd_h_kernel, 2, , 2);
+            else if ((a.e.io_f16 & 3) == 1) HY_TILES_01(conv_fwd_h_kernel, , 1);
+            else if ((a.e.io_f16 & 3) == 2) HY_TILES_01(conv_fwd_h_kernel, , 2);
+            else HY_TILES_01(conv_fwd_h_kernel, , 3);
+            return HY_LAUNCH_CHECK("conv_fwd_h_kernel");
+        case ConvGemm::F16:
+            HY_TILES_01(conv_fwd_kernel, , true);
+            return HY_LAUNCH_CHECK("conv_fwd_kernel(f16)");
+        case ConvGemm::B6DB:
+            if constexpr (TM == 1 && TN == 1 && WM_ == 2 && WN_ == 2) {  // choose_gemm: tile 4 only
+                HY_TILES_01(conv_fwd_b6db_kernel, );
+                return HY_LAUNCH_CHECK("conv_fwd_b6db_kernel");
+            }
+            [[fallthrough]];
+        case ConvGemm::B6:
+            HY_TILES_01(conv_fwd_b6_kernel, );
+            return HY_LAUNCH_CHECK("conv_fwd_b6_kernel");
+        case ConvGemm::F32: break;
+    }
+    if (r.mode == 2) HY_TILES(conv_fwd_kernel, 2, );
+    else HY_TILES_01(conv_fwd_kernel, );
+#undef HY_TILES_01
+#undef HY_TILES
+    return HY_LAUNCH_CHECK("conv_fwd_kernel");
+}
+
+static int launch_tiles(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    int rc;
+    switch (r.tile) {
+        case 0: rc = launch_fwd<2, 2, 2, 2>(a, r, st); break;
+        case 1: rc = launch_fwd<2, 1, 2, 2>(a, r, st); break;
+        case 3: rc = launch_fwd<1, 2, 2, 2>(a, r, st); break;
+        case 4: rc = launch_fwd<1, 1, 2, 2>(a, r, st); break;
+        default: rc = launch_fwd<1, 1, 4, 1>(a, r, st); break;
+    }
+    if (rc || a.nsplit == 1) return rc;
+    const long long total = (long long)a.M * a.g.Co * a.g.nphase;
+    const bool yh = (a.e.io_f16 & 2) != 0;
+    if (a.vec4) {
+        const dim3 grid((int)std::min<long long>((total / 4 + 255) / 256, 8192));
+        if (yh) hipLaunchKernelGGL(conv_splitk_reduce4_kernel<true>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(conv_splitk_reduce4_kernel<false>, grid, dim3(256), 0, st, a);
+        return HY_LAUNCH_CHECK("conv_splitk_reduce4_kernel");
+    }
+    const dim3 grid((int)std::min<long long>((total + 255) / 256, 8192));
+    if (yh) hipLaunchKernelGGL(conv_splitk_reduce_kernel<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, grid, dim3(256), 0, st, a);
+    return HY_LAUNCH_CHECK("conv_splitk_reduce_kernel");
+}
+
+extern "C" {
 
 int hyres_conv_tuning(int key, int value, int* old) {
     HY_REQUIRE(key >= 0 && key < HYRES_TUNE_KEYS, HYRES_E_ARG, "conv_tuning: key %d", key);
@@ -3520,23 +3589,22 @@ int hyres_conv_tuning(int key, int value, int* old) {
 
 long long hyres_conv_workspace_bytes(const hyres_conv_geom* g) {
     // the larger of the fp32 and fp16-operand plans (the tile, hence the split, depends on the dtype)
-    if (!g || narrow_ok(g)) return 0;
+    if (!g) return 0;
     long long need = 0;
     for (int f16 = 0; f16 < 2; ++f16) {
         hyres_epilogue e{};
         e.kind = HYRES_EPI_BIAS;
         e.f16_operands = f16;
-        need = std::max(need, plan_ws_bytes(g, conv_plan(g, choose_conv(g, &e, true).tile)));
+        need = std::max(need, split_ws_bytes(g, route(g, &e, ConvFacts::ideal()).nsplit));
     }
     return need;
 }
 
 int hyres_conv_plan(const hyres_conv_geom* g, const hyres_epilogue* e, int* tile, int* nsplit) {
     HY_REQUIRE(g && e, HYRES_E_ARG, "conv_plan: NULL argument");
-    const ConvChoice ch = choose_conv(g, e, true);
-    const ConvPlan p = ch.narrow ? ConvPlan{1, 0} : conv_plan(g, ch.tile);
-    if (tile) *tile = ch.narrow ? -1 : ch.tile;
-    if (nsplit) *nsplit = p.nsplit;
+    const ConvRoute r = route(g, e, ConvFacts::ideal());
+    if (tile) *tile = r.family == ConvFamily::NARROW ? -1 : r.tile;
+    if (nsplit) *nsplit = r.nsplit;
     return ok();
 }
 
@@ -3545,53 +3613,47 @@ int hyres_conv_forward(const hyres_conv_geom* g, const float* x, const float* w2
     HY_REQUIRE(g && x && w2 && y && e, HYRES_E_ARG, "conv_forward: NULL argument");
     HY_REQUIRE(g->nphase >= 1 && g->nphase <= 4 && g->Ci > 0 && g->Co > 0, HYRES_E_SHAPE, "conv: bad geom");
     HY_REQUIRE(ldw >= g->ntaps * g->Ci, HYRES_E_SHAPE, "conv: ldw %d < ntaps*Ci %d", ldw, g->ntaps * g->Ci);
+    ConvFacts f;
+    f.xw16 = aligned16(x) && aligned16(w2) && g->ldx % 4 == 0 && ldw % 4 == 0;
+    {
+        auto al = [](const void* p, int ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); };
+        // HYRES_EPI_SA_BWD reads aux0 ([P][2]) and aux2 (argmax), HYRES_EPI_ROWSCALE aux1 (the scale), one scalar per
+        // pixel: no alignment needed
+        const bool sa = e->kind == HYRES_EPI_SA_BWD, rs = e->kind == HYRES_EPI_ROWSCALE;
+        f.vec4 = g->Co % 4 == 0 && al(y, g->ldy) && al(e->bias, 4) && al(e->res, e->ldres) && al(e->out2, e->ldo2) &&
+                 (sa || al(e->aux0, e->ld0)) && (rs || al(e->aux1, e->ld1)) && (sa || al(e->aux2, e->ld2));
+    }
+    f.rsrc_ok = epi_span_ok(g, e);
+    f.y8 = aligned8(y);
+    f.opnd8 = aligned8(e->res) && aligned8(e->aux0) && aligned8(e->out2);
+    f.ws_bytes = ws ? ws_bytes : 0;
+    f.ws16 = aligned16(ws);
+    const ConvRoute r = route(g, e, f);
+    const int mode = r.mode;
     ConvArgs a;
     a.g = *g; a.x = x; a.w2 = w2; a.ldw = ldw; a.y = y; a.e = *e;
     a.M = g->B * g->Hq * g->Wq;
     a.xcd = 1;
     a.prio = 1;
     a.b6sw = g_tune[19] != 0;
-    const ConvChoice ch = choose_conv(g, e, aligned16(x) && aligned16(w2) && g->ldx % 4 == 0 && ldw % 4 == 0);
-    ConvPlan plan = conv_plan(g, ch.tile);
-    a.nsplit = 1;
-    a.cps = 0;
-    a.slab = nullptr;
-    {
-        auto al = [](const void* p, int ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); };
-        // HYRES_EPI_SA_BWD reads aux0 ([P][2]) and aux2 (argmax), HYRES_EPI_ROWSCALE aux1 (the scale), one scalar per
-        // pixel: no alignment needed
-        const bool sa = e->kind == HYRES_EPI_SA_BWD, rs = e->kind == HYRES_EPI_ROWSCALE;
-        a.vec4 = g->Co % 4 == 0 && al(y, g->ldy) && al(e->bias, 4) && al(e->res, e->ldres) && al(e->out2, e->ldo2) &&
-                 (sa || al(e->aux0, e->ld0)) && (rs || al(e->aux1, e->ld1)) && (sa || al(e->aux2, e->ld2));
-    }
-    {
-        const long long npo = (long long)g->B * g->Ho * g->Wo;
-        const int ld = std::max(g->ldy, std::max(e->res ? e->ldres : 0, e->aux0 ? e->ld0 : 0));
-        a.rsrc_ok = npo * ld * 4 < 0x7FFFFFF0LL;
-    }
-    const long long need = plan_ws_bytes(g, plan);
-    if (!ch.narrow && plan.nsplit > 1 && ws && ws_bytes >= need) {  // without workspace: single pass (correct, slower)
-        a.nsplit = plan.nsplit;
-        a.cps = plan.cps;
-        a.slab = (float*)ws;
-        if (!aligned16(ws)) a.vec4 = 0;
-    }
+    a.vec4 = r.vec4;
+    a.rsrc_ok = f.rsrc_ok;
+    a.x_bytes = r.x_bytes;
+    a.nsplit = r.family == ConvFamily::TILES ? r.nsplit : 1;
+    a.cps = r.cps;
+    a.slab = r.nsplit > 1 ? (float*)ws : nullptr;
     {
         const long long wb = (long long)g->Co * ldw * 4;
         const long long img_bytes = (long long)g->Hi * g->Wi * g->ldx * 4;
-        HY_REQUIRE(wb < 0x7FFFFFF0LL && 3 * img_bytes < 0x7FFFFFF0LL && (long long)g->Ho * g->Wo * g->ldy < 0x7FFFFFFFLL,
+        HY_REQUIRE(fits32(wb) && fits32(3 * img_bytes) && (long long)g->Ho * g->Wo * g->ldy < 0x7FFFFFFFLL,
                    HYRES_E_SHAPE, "conv: per-image tensor too large for 32-bit offsets");
         a.w_bytes = (int)wb;
     }
-    int mode;
-    if (g->Ci % KT == 0) {
-        HY_REQUIRE(aligned16(x) && aligned16(w2) && g->ldx % 4 == 0 && ldw % 4 == 0, HYRES_E_ALIGN,
-                   "conv: vector path needs 16B-aligned x/w2 and ldx,ldw %% 4 == 0");
-        mode = e->square_input ? 1 : 0;
+    if (mode != 2) {
+        HY_REQUIRE(f.xw16, HYRES_E_ALIGN, "conv: vector path needs 16B-aligned x/w2 and ldx,ldw %% 4 == 0");
     } else {
         HY_REQUIRE(g->nphase == 1 && !e->square_input, HYRES_E_SHAPE,
                    "conv: Ci %% 32 != 0 supported only single-phase, no square");
-        mode = 2;
     }
     if (e->kind == HYRES_EPI_GDN || e->kind == HYRES_EPI_IGDN)
         HY_REQUIRE(e->aux0 && e->out2, HYRES_E_ARG, "conv: GDN epilogue needs aux0/out2");
@@ -3605,7 +3667,8 @@ int hyres_conv_forward(const hyres_conv_geom* g, const float* x, const float* w2
                                                          || (e->io_f16 & 2)),
                    HYRES_E_ARG, "conv: a fp16 GDN-backward epilogue needs fp16 Y (its operands share Y's dtype)");
         HY_REQUIRE(!(e->io_f16 & 1) || mode != 2, HYRES_E_ARG, "conv: fp16 X needs Ci %% 32 == 0");
-        HY_REQUIRE(!ch.narrow || !(e->io_f16 & 2), HYRES_E_ARG, "conv: the Co <= 4 kernel writes fp32 only");
+        HY_REQUIRE(r.family != ConvFamily::NARROW || !(e->io_f16 & 2), HYRES_E_ARG,
+                   "conv: the Co <= 4 kernel writes fp32 only");
     }
     if (e->act == HYRES_ACT_RELU_MASK)
         HY_REQUIRE(e->aux0 && e->kind == HYRES_EPI_BIAS, HYRES_E_ARG, "conv: ReLU mask needs aux0, BIAS epilogue");
@@ -3619,7 +3682,7 @@ int hyres_conv_forward(const hyres_conv_geom* g, const float* x, const float* w2
                        !e->out2 && e->io_f16 == 0 && !e->f16_operands && e->ld2 >= HYRES_PRELU_PARTIALS,
                    HYRES_E_ARG, "conv: PReLU mask needs aux0 (pre-activation), aux1 (slope gradient), aux2 (>= %d "
                    "partials), slope; BIAS, no accumulate / out2, fp32", HYRES_PRELU_PARTIALS);
-        HY_REQUIRE(mode == 0 && a.vec4 && wres32_ok(g, e) && wres_bf6() &&
+        HY_REQUIRE(r.family == ConvFamily::WRES32 && wres_bf6() &&
                        wres_blocks(g->Co / 32) * (g->Co / 32) <= HYRES_PRELU_PARTIALS,
                    HYRES_E_ARG, "conv: the PReLU-mask epilogue runs on conv3x3_wres_bf6_kernel only");
     }
@@ -3632,150 +3695,64 @@ int hyres_conv_forward(const hyres_conv_geom* g, const float* x, const float* w2
                        (!(e->io_f16 & 2) || stream_hf_cfg(g, e)),
                    HYRES_E_ARG, "conv: SA_BWD needs aux0 ([P][ld0 >= 2]) and aux2 (argmax), no act / res / out2, fp32 Y "
                    "(fp16 Y: conv1x1_stream_hf_kernel's 64 -> 192 only)");
-    hipStream_t st = as_stream(s);
-    if (ch.narrow) {
-        a.nsplit = 1;
-        dim3 grid(ceil_div(a.M, NARROW_PIX), g->nphase);
-        switch (g->Co) {
-            case 1: launch_narrow<1>(a, grid, st); break;
-            case 2: launch_narrow<2>(a, grid, st); break;
-            case 3: launch_narrow<3>(a, grid, st); break;
-            default: launch_narrow<4>(a, grid, st); break;
-        }
-        return HY_LAUNCH_CHECK("conv_narrow_kernel");
-    }
-    if (mode == 0 && a.vec4 && wres32_ok(g, e)) {
-        a.nsplit = 1;
-        return launch_wres32(a, st);
-    }
-    if (mode == 0 && a.vec4 && halo16_ok(g, e)) {
-        a.nsplit = 1;
-        return wres16_ok(g) ? launch_wres16(a, st) : launch_halo16(a, st);
-    }
-    {
-        const int cfg = stream_b6_cfg(g, e);
-        const long long xb = (long long)a.M * g->ldx * 4;
-        if (cfg && mode == 0 && a.vec4 && a.rsrc_ok && xb < 0x7FFFFFF0LL && aligned16(x) && aligned16(w2) &&
-            ldw % 4 == 0) {
-            a.x_bytes = (int)xb;
-            a.nsplit = 1;
-            return launch_stream_b6(a, cfg, st);
-        }
-    }
-    {
-        const int nt = stream_nt(g, e);
-        const long long xb = (long long)a.M * g->ldx * 4;
-        if (nt && mode == 0 && a.vec4 && xb < 0x7FFFFFF0LL && aligned16(x) && aligned16(w2) && ldw % 4 == 0) {
-            a.x_bytes = (int)xb;
-            a.nsplit = 1;
-            return launch_stream(a, nt, g->Ci / 8, 0, st);
-        }
-    }
-    {
-        const int cfg = stream_hf_cfg(g, e);
-        const long long xb = (long long)a.M * g->ldx * 2;
-        if (cfg && mode == 0 && a.rsrc_ok && xb < 0x7FFFFFF0LL && aligned16(x) && aligned16(w2) && ldw % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(e->res) & 7) == 0 &&
-            (reinterpret_cast<uintptr_t>(e->aux0) & 7) == 0 && (reinterpret_cast<uintptr_t>(e->out2) & 7) == 0) {
-            a.x_bytes = (int)xb;
-            a.nsplit = 1;
-            return launch_stream_hf(a, cfg, st);
-        }
-    }
     // no other kernel implements SA_BWD with an fp16 Y (its epi_store4 instantiations leave the case out)
-    HY_REQUIRE(!(e->kind == HYRES_EPI_SA_BWD && ((e->io_f16 & 2) || e->act == HYRES_ACT_PRELU_MASK)), HYRES_E_ARG,
-               "conv: an fp16-Y or PReLU-mask SA_BWD input-gradient needs the streaming kernels (alignment / size / "
-               "split mode)");
-    {
-        const int nt = stream_h_nt(g, e);
-        const long long xb = (long long)a.M * g->ldx * 2;
-        if (nt && mode == 0 && xb < 0x7FFFFFF0LL && aligned16(x) && aligned16(w2) && ldw % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(y) & 7) == 0) {
-            a.x_bytes = (int)xb;
-            a.nsplit = 1;
-            return launch_stream_h(a, nt, g->Ci / 16, st);
-        }
+    if (r.family == ConvFamily::STREAM_H || r.family == ConvFamily::TILES)
+        HY_REQUIRE(!(e->kind == HYRES_EPI_SA_BWD && ((e->io_f16 & 2) || e->act == HYRES_ACT_PRELU_MASK)), HYRES_E_ARG,
+                   "conv: an fp16-Y or PReLU-mask SA_BWD input-gradient needs the streaming kernels (alignment / size / "
+                   "split mode)");
+    hipStream_t st = as_stream(s);
+    switch (r.family) {
+        case ConvFamily::NARROW: return launch_narrow_co(a, r, st);
+        case ConvFamily::WRES32: return launch_wres32(a, st);
+        case ConvFamily::WRES16: return launch_wres16(a, st);
+        case ConvFamily::HALO16: return launch_halo16(a, st);
+        case ConvFamily::STREAM_B6: return launch_stream_b6(a, r.cfg, st);
+        case ConvFamily::STREAM: return launch_stream(a, r.cfg, st);
+        case ConvFamily::STREAM_HF: return launch_stream_hf(a, r.cfg, st);
+        case ConvFamily::STREAM_H: return launch_stream_h(a, r.cfg, st);
+        case ConvFamily::TILES: break;
     }
-    int rc;
-    switch (ch.tile) {
-        case 0: rc = launch_fwd<2, 2, 2, 2>(a, mode, st); break;
-        case 1: rc = launch_fwd<2, 1, 2, 2>(a, mode, st); break;
-        case 3: rc = launch_fwd<1, 2, 2, 2>(a, mode, st); break;
-        case 4: rc = launch_fwd<1, 1, 2, 2>(a, mode, st); break;
-        default: rc = launch_fwd<1, 1, 4, 1>(a, mode, st); break;
-    }
-    if (rc || a.nsplit == 1) return rc;
-    long long total = (long long)a.M * g->Co * g->nphase;
-    const bool yh = (e->io_f16 & 2) != 0;
-    if (a.vec4) {
-        int blocks = (int)std::min<long long>((total / 4 + 255) / 256, 8192);
-        if (yh) hipLaunchKernelGGL(conv_splitk_reduce4_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(conv_splitk_reduce4_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
-        return HY_LAUNCH_CHECK("conv_splitk_reduce4_kernel");
-    }
-    int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-    if (yh) hipLaunchKernelGGL(conv_splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
-    return HY_LAUNCH_CHECK("conv_splitk_reduce_kernel");
+    return launch_tiles(a, r, st);
 }
 
 int hyres_conv_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, int split, char* buf, int n) {
     HY_REQUIRE(g && e && buf && n > 0, HYRES_E_ARG, "conv_kernel_name: bad args");
-    const ConvChoice ch = choose_conv(g, e, true);
-    if (ch.narrow) {
-        snprintf(buf, n, "%s<%d, %d>", narrow_strip_ok(g) ? "conv_narrow_strip_kernel" : "conv_narrow_kernel",
-                 std::min(g->Co, 4), g->Ci == 64 ? 1 : 2);
-        return 0;
-    }
-    if (ch.mode == 0 && wres32_ok(g, e)) {
-        snprintf(buf, n, wres_bf6() ? "conv3x3_wres_bf6_kernel" : "conv3x3_wres_f32_kernel");
-        return 0;
-    }
-    if (ch.mode == 0 && halo16_ok(g, e)) {
-        snprintf(buf, n, "%s<%d>", wres16_ok(g) ? "conv3x3_wres_f16_kernel" : "conv3x3_halo_f16_kernel", e->io_f16 & 3);
-        return 0;
-    }
-    {
-        const int cfg = stream_b6_cfg(g, e);
-        if (cfg && ch.mode == 0) {
-            snprintf(buf, n, "conv1x1_stream_b6_kernel<%d, %d, %d, %s>", cfg & 15, (cfg >> 4) & 15, cfg >> 8,
-                     g_tune[11] == 0 ? "false" : "true");
-            return 0;
-        }
-    }
-    {
-        const int nt = stream_nt(g, e);
-        if (nt && ch.mode == 0) {
-            snprintf(buf, n, "conv1x1_stream_kernel<%d, %d%s>", nt, g->Ci / 8, e->f16_operands ? ", true" : "");
-            return 0;
-        }
-        const int chf = stream_hf_cfg(g, e);
-        if (chf && ch.mode == 0) {
-            snprintf(buf, n, "conv1x1_stream_hf_kernel<%d, %d, %d>", chf & 15, (chf >> 4) & 15, chf >> 8);
-            return 0;
-        }
-        const int nth = stream_h_nt(g, e);
-        if (nth && ch.mode == 0) {  // (the launch also checks pointer alignment; the label assumes it)
-            snprintf(buf, n, "conv1x1_stream_h_kernel<%d, %d>", nth, g->Ci / 16);
-            return 0;
-        }
-    }
     static const char* tiles[5] = {"2, 2, 2, 2", "2, 1, 2, 2", "1, 1, 4, 1", "1, 2, 2, 2", "1, 1, 2, 2"};
-    const bool f16 = e->f16_operands && ch.mode != 2;
-    if (e->io_f16 & 3) {
-        snprintf(buf, n, "conv_fwd_h_kernel<%s, %d, %s, %d>", tiles[ch.tile], ch.mode, split ? "true" : "false",
-                 e->io_f16 & 3);
-        return 0;
+    const ConvRoute r = route(g, e, ConvFacts::ideal());
+    const int nt = cfg_nt(r.cfg), k = cfg_k(r.cfg), f = cfg_f(r.cfg), io = e->io_f16 & 3;
+    const char* sp = split ? "true" : "false";
+    switch (r.family) {
+        case ConvFamily::NARROW:
+            snprintf(buf, n, "%s<%d, %d>", r.strip ? "conv_narrow_strip_kernel" : "conv_narrow_kernel",
+                     std::min(g->Co, 4), g->Ci == 64 ? 1 : 2);
+            break;
+        case ConvFamily::WRES32:
+            snprintf(buf, n, wres_bf6() ? "conv3x3_wres_bf6_kernel" : "conv3x3_wres_f32_kernel");
+            break;
+        case ConvFamily::WRES16: snprintf(buf, n, "conv3x3_wres_f16_kernel<%d>", io); break;
+        case ConvFamily::HALO16: snprintf(buf, n, "conv3x3_halo_f16_kernel<%d>", io); break;
+        case ConvFamily::STREAM_B6:
+            snprintf(buf, n, "conv1x1_stream_b6_kernel<%d, %d, %d, %s>", nt, k, f, stream_b6_ce() ? "true" : "false");
+            break;
+        case ConvFamily::STREAM:
+            snprintf(buf, n, "conv1x1_stream_kernel<%d, %d%s>", nt, k, e->f16_operands ? ", true" : "");
+            break;
+        case ConvFamily::STREAM_HF: snprintf(buf, n, "conv1x1_stream_hf_kernel<%d, %d, %d>", nt, k, f); break;
+        case ConvFamily::STREAM_H: snprintf(buf, n, "conv1x1_stream_h_kernel<%d, %d>", nt, k); break;
+        case ConvFamily::TILES:
+            switch (r.gemm) {
+                case ConvGemm::H:
+                    snprintf(buf, n, "conv_fwd_h_kernel<%s, %d, %s, %d>", tiles[r.tile], r.mode, sp, io);
+                    break;
+                case ConvGemm::B6DB:
+                    snprintf(buf, n, "conv_fwd_b6db_kernel<%s, %d, %s>", tiles[r.tile], r.mode, sp);
+                    break;
+                case ConvGemm::B6: snprintf(buf, n, "conv_fwd_b6_kernel<%s, %d, %s>", tiles[r.tile], r.mode, sp); break;
+                default:
+                    snprintf(buf, n, "conv_fwd_kernel<%s, %d, %s, %s>", tiles[r.tile], r.mode, sp,
+                             r.gemm == ConvGemm::F16 ? "true" : "false");
+            }
     }
-    if (g_tune[7] == 1 && !f16 && ch.mode != 2) {
-        const long long M = (long long)g->B * g->Hq * g->Wq;
-        const bool db = ch.tile == 4 && (g_tune[20] == 1 || (g_tune[20] < 0 && M <= 16384));
-        snprintf(buf, n, "%s<%s, %d, %s>", db ? "conv_fwd_b6db_kernel" : "conv_fwd_b6_kernel", tiles[ch.tile], ch.mode,
-                 split ? "true" : "false");
-        return 0;
-    }
-    snprintf(buf, n, "conv_fwd_kernel<%s, %d, %s, %s>", tiles[ch.tile], ch.mode, split ? "true" : "false",
-             f16 ? "true" : "false");
     return 0;
 }
 

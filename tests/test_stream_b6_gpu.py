@@ -29,7 +29,16 @@ def _rand(shape, seed, scale=1.0):
     return (torch.rand(shape, generator=g) * 2 - 1) * scale
 
 
-def _run(Ci, Co, F, act, out2, stream_on, ce=1):
+def _off8(t):
+    """A copy of t whose base lies 8 bytes past a 16-byte boundary (two floats into a larger allocation)."""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    v = buf[2:2 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 8
+    return v
+
+
+def _run(Ci, Co, F, act, out2, stream_on, ce=1, misalign=False):
     from hyres_hip import _lib as L
     from hyres_hip import ops as O
     D = dev()
@@ -43,6 +52,8 @@ def _run(Ci, Co, F, act, out2, stream_on, ce=1):
     old = _rand((P, Co), 6).to(D)
     slope = torch.full((1,), 0.25, device=D)
     y = old.clone() if F & 4 else torch.full((P, Co), float("nan"), device=D)
+    if misalign:
+        y, res = _off8(y), _off8(res)
     pre = torch.full((P, Co), float("nan"), device=D)
     g = O._geom("hyres_geom_conv2d", B, H, W, Ci, Ci, Co, Co, 1, 1, 1, 0, 1)
     w2 = torch.empty((Co, Ci), device=D)
@@ -105,6 +116,19 @@ def test_stream_b6_matches_fp64(Ci, Co, F):
     assert not name_t.startswith("conv1x1_stream_b6"), name_t
     for err in (err_s, err_m):
         assert err < 2e-6 and err <= 2 * err_t + 1e-9
+
+
+def test_stream_b6_misaligned_operands_take_the_tiles():
+    """y and res 8 bytes past a 16-byte boundary: the launcher routes on the real pointers (vec4 false), so the call
+    leaves the streaming kernel for the tiled implicit GEMM and succeeds; the label, which assumes aligned operands,
+    cannot show this half of the route. Bar: no worse than twice the aligned tiled call (hyres_conv_tuning key 10 = 0)
+    on the same data."""
+    from hyres_hip import _lib as L
+    name_u, err_u = _run(64, 64, 1, L.ACT_RELU, False, True, misalign=True)
+    name_t, err_t = _run(64, 64, 1, L.ACT_RELU, False, False)
+    print(f"64->64 F=1 misaligned y/res: {name_u} {err_u:.2e}, aligned tiles {name_t} {err_t:.2e}")
+    assert not name_t.startswith("conv1x1_stream_b6"), name_t
+    assert err_u <= 2 * err_t + 1e-9, (err_u, err_t)
 
 
 def _run_sab(acc, stream_on):
