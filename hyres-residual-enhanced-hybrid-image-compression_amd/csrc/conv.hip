@@ -3001,18 +3001,6 @@ static int cfg_nt(int cfg) { return cfg & 15; }
 static int cfg_k(int cfg) { return (cfg >> 4) & 255; }
 static int cfg_f(int cfg) { return cfg >> 12; }
 
-static int g_cus = 0;
-static int num_cus() {
-    if (!g_cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                     hipSuccess || n < 1)
-            n = 256;
-        g_cus = n;
-    }
-    return g_cus;
-}
-
 static long long gemm_rows(const hyres_conv_geom* g) { return (long long)g->B * g->Hq * g->Wq; }
 
 static int max_taps(const hyres_conv_geom* g) {

@@ -18,6 +18,19 @@ extern int g_tune[HYRES_TUNE_KEYS];
 // fp32 GEMMs on the bf16 MFMA (hyres_conv_tuning key 7 = 1, the default): "bf16x6"
 inline bool f32_gemm_bf6() { return g_tune[7] == 1; }
 
+// compute units of the current device (256 on an MI355X, and 256 without a device: the host-only queries)
+inline int num_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
+                                                     hipSuccess || n < 1)
+            n = 256;
+        cus = n;
+    }
+    return cus;
+}
+
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 

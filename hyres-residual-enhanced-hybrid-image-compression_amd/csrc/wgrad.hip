@@ -2155,13 +2155,29 @@ using namespace hyres;
 
 namespace hyres {
 
+// ------------------------------------------------------------------------------------------------
+// kernel choice: wgrad_route() decides the kernel and its template arguments, the split plan, the launch
+// dims and the workspace layout; wgrad_issue launches what it says, hyres_wgrad_kernel_name /
+// hyres_wgrad_plan / hyres_wgrad_workspace_bytes report it. The predicates below are each written once.
+// ------------------------------------------------------------------------------------------------
+enum class WgradFamily { GENERIC, F16, ONE, ONE_B6, ONE_B6_PF2, THIN, HALO, HALO_F16, HALO_B6, HALO_B6_PF2 };
 
-struct WgradPlan {
-    int TMc, TNc, WMc, WNc, NT, BM, BN, mtiles, ntiles, ngroups, nchunks, nsplit, cps, tapn, nblocks;
-    int halo, hk, hdh, hdw, hdil;  // wgrad_halo_kernel: K, first tap's (dh, dw), tap spacing
-    int g1x1;                      // wgrad1x1_kernel: 4-wave groups per block
-    int hg;                        // wgrad_halo(_f16)_kernel: 4-wave groups per block
+// What wgrad_route() needs to know beyond the desc: wgrad_issue fills it from the real pointers, the host-only
+// queries assume ideal()
+struct WgradFacts {
+    bool p16, q16;  // the caller's P / Q 16-byte aligned
+    bool ws16;      // the workspace 16-byte aligned (the fp32 copies of fp16 operands live in it)
+    static WgradFacts ideal() { return {true, true, true}; }
 };
+
+// taps folded into the column dimension (the 3-channel layers)
+static bool tap_folded(const hyres_wgrad_desc* d) { return d->N <= 16 && d->ntaps > 1 && !d->square_q; }
+
+// plain 1x1: one tap (0, 0) on Q's own grid, no square (one tap: one tap group, no tap folding)
+static bool plain_1x1(const hyres_wgrad_desc* d) {
+    return !d->square_q && d->ntaps == 1 && d->dh[0] == 0 && d->dw[0] == 0 && d->sq == 1 && d->Hqq == d->Hq &&
+           d->Wqq == d->Wq;
+}
 
 // wgrad_halo_kernel applies: fp32, dense KxK taps (K = 3 or 5, dilation 1; K = 3 with dilation 2), Q stride
 // 1 or 2 (5x5 only), base rows of a multiple of 32 pixels, both operands >= 32 channels on the float4 path.
@@ -2180,107 +2196,9 @@ static bool halo_ok(const hyres_wgrad_desc* d, int* K, int* dil) {
     return true;
 }
 
-static bool wgrad_f16_ok(const hyres_wgrad_desc* d);
-
-static WgradPlan wgrad_plan(const hyres_wgrad_desc* d) {
-    WgradPlan p{};
-    p.NT = 1;
-    int hk = 0, hdil = 1;
-    const bool halo = halo_ok(d, &hk, &hdil);  // fp32 or (AMP) f16 halo kernel: 32-pixel chunks either way
-    const int kt = (wgrad_f16_ok(d) && !halo) ? KTH : KT;
-    p.tapn = (d->N <= 16 && d->ntaps > 1 && !d->square_q) ? 1 : 0;
-    const int ncols = p.tapn ? d->ntaps * d->N : d->N;
-    if (p.tapn) {
-        if (ncols <= 32) { p.TMc = 1; p.TNc = 1; p.WMc = 4; p.WNc = 1; }
-        else { p.TMc = 1; p.TNc = 1; p.WMc = 2; p.WNc = 2; }
-    } else if (d->M >= 128 && d->N >= 128) { p.TMc = 2; p.TNc = 2; p.WMc = 2; p.WNc = 2; }
-    else if (d->M >= 128 && d->N >= 64 && d->ntaps == 1) { p.TMc = 2; p.TNc = 1; p.WMc = 2; p.WNc = 2; }
-    else if (d->M <= 32) { p.TMc = 1; p.TNc = 1; p.WMc = 1; p.WNc = 4; }
-    else if (d->N <= 32) { p.TMc = 1; p.TNc = 1; p.WMc = 4; p.WNc = 1; }
-    else {
-        p.TMc = 1; p.TNc = 1; p.WMc = 2; p.WNc = 2;
-        // fp32: group 9 / 5 taps per block (operand reuse); f16: one tap per block column group (measured
-        // faster on every f16 geometry of the step: the f16 main loop is short, more blocks hide it better)
-        p.NT = (d->ntaps % 9 == 0) ? 9 : (d->ntaps % 5 == 0) ? 5 : 1;
-        if (kt == KTH || g_tune[5] == 1) p.NT = 1;
-    }
-    p.BM = 32 * p.TMc * p.WMc; p.BN = 32 * p.TNc * p.WNc;
-    p.mtiles = ceil_div(d->M, p.BM); p.ntiles = ceil_div(ncols, p.BN);
-    p.ngroups = p.tapn ? 1 : ceil_div(d->ntaps, p.NT);
-    p.nchunks = ceil_div((long long)d->B * d->Hq * d->Wq, kt);
-    if (halo) {
-        p.halo = 1;
-        p.hk = hk;
-        p.hdil = hdil;
-        p.hdh = d->dh[0];
-        p.hdw = d->dw[0];
-        p.tapn = 0;
-        p.TMc = p.TNc = 1; p.WMc = p.WNc = 2;
-        p.BM = p.BN = 64;
-        p.mtiles = ceil_div(d->M, 64); p.ntiles = ceil_div(d->N, 64);
-        // 3x3: one kernel row of 3 taps per block, or all 9 taps per block (one 3-row halo per chunk) — rows of 3
-        // give 3x the tiles, so a third of the pixel splits and of the split slab for the same grid. Default: rows
-        // for dilation 1 (AMP step 21.56 -> 21.34 ms, fp32 42.82 -> 42.68 ms over 3 alternating repeats each;
-        // 128^2 fp32 kernel 235 -> 208 us), all 9 taps for the dilated 3x3s (256^2: 678 vs 797 us fp32, 152 vs 219 us
-        // f16: their halo rows are 2 apart, so a row group re-stages most of the chunk; profiles/r3r_rows_ab.txt,
-        // r3y_rows_fp32_ab.txt)
-        const int rows = hdil == 2 ? 3 : 1;
-        p.NT = p.hk == 3 ? (rows == 1 ? 3 : 9) : 5;
-        p.ngroups = d->ntaps / p.NT;
-    }
-    const long long tiles = (long long)p.mtiles * p.ntiles * p.ngroups;
-    // ~2048 blocks (swept on MI355X: 1024 -> 2048 is -0.6 % step time; fewer splits hurt), >= 8 chunks
-    // (256 pixels; f16: 4 chunks of 64) per split, <= 512 splits (hyres_conv_tuning keys 3, 4, 6 override them for
-    // sweeps). Small grids (<= 16384 pixels, the 32^2 region at
-    // bs 16): ~4096 blocks, fp32 multi-tap splits down to 4 chunks. The split count is capped so that the partial
-    // slab stays <= 16 M floats (64 MB): for the wide 1x1 layers (M x N ~ 0.5 M) the slab write + reduce
-    // otherwise costs more than the parallelism buys (scripts/tile_sweep.py --wgrad)
-    const long long Q = (long long)d->B * d->Hq * d->Wq;
-    const bool small = Q <= 16384;
-    const int tb = g_tune[3] > 0 ? g_tune[3] : (small ? 4096 : 2048);
-    const int mc0 = g_tune[4] > 0 ? g_tune[4] : ((small && kt == KT && d->ntaps > 1) ? 4 : 8);
-    const int mc = std::max(1, mc0 * KT / kt);
-    // <= 256 splits (<= 64 on the small grids): past that the split slab's write + reduce costs more than the
-    // extra blocks buy — step 32.79 -> 32.54 ms, AMP 19.10 -> 18.76 ms against 512 everywhere (isolated, kernel +
-    // reduce: 128^2 3x3 64->64 143 -> 137 us, 32^2 3x3 96->96 51.6 -> 43.4 us; one exception measured, 256^2 1x1
-    // 64->64 132 -> 160 us, but 512 splits for the 1x1s only gave no step gain; profiles/r5z_wgrad_split_ab.txt)
-    const int ms = g_tune[6] > 0 ? g_tune[6] : (small ? 64 : 256);
-    const long long slab_cap = std::max<long long>(4, (16LL << 20) / ((long long)d->ntaps * d->M * d->N));
-    const long long want = std::min<long long>(std::max<long long>(1, (tb + tiles - 1) / tiles), slab_cap);
-    const long long maxsplit = std::max<long long>(1, p.nchunks / mc);
-    p.nsplit = (int)std::min<long long>(std::min<long long>(want, maxsplit), ms);
-    if (p.halo) {
-        // whole rounds only: the halo kernel runs 2 blocks per CU (3 for 5x5 stride 1); a partial last round
-        // of long split-K blocks costs as much as a full one, so drop it (e.g. 800 -> 500 blocks)
-        // (the bf16x6 kernel: 1 block per CU when it stages all 9 taps' halo, 158 KB of LDS)
-        const bool b6_9 = f32_gemm_bf6() && !wgrad_f16_ok(d) && p.NT == 9;
-        const long long cap = 256LL * (b6_9 ? 1 : (p.hk == 5 && d->sq == 1) ? 3 : 2);
-        if (tiles * p.nsplit > cap) p.nsplit = (int)std::max<long long>(1, (tiles * p.nsplit / cap) * cap / tiles);
-        // and fill a partial single round when that grows the slab by <= 25 % (128^2 3x3: 455 -> 512)
-        else if (cap / tiles <= maxsplit && 4 * (cap / tiles) <= 5LL * p.nsplit) p.nsplit = (int)(cap / tiles);
-    }
-    // 1x1 stride-1 fp32 gradients (wgrad1x1_kernel) outside the small grids: 2 groups of 4 waves per block share
-    // one split's pixels, so the same waves write half the slab. Isolated 128^2 64<->128: 65 -> 62 us; on the 32^2
-    // grids it lost (24.6 -> 30.5 us: half the blocks). (Two groups per block for the halo kernels — half their
-    // split slab — won isolated but lost in the live step, 40.0 -> 41.1 ms: the 146 KB block keeps the concurrent
-    // branches' blocks off its CU; profiles/r3o_halo_groups.txt. Removed in round 4.)
-    p.hg = 1;
-    p.g1x1 = 1;
-    if (!small && !halo && kt == KT && !f32_gemm_bf6() && !p.tapn && !d->square_q && d->ntaps == 1 && d->dh[0] == 0 &&
-        d->dw[0] == 0 && d->sq == 1 && d->Hqq == d->Hq && d->Wqq == d->Wq && p.ngroups == 1 && p.nsplit >= 2) {
-        p.g1x1 = 2;
-        p.nsplit = (p.nsplit + 1) / 2;
-    }
-    p.cps = ceil_div(p.nchunks, p.nsplit);
-    p.nsplit = ceil_div(p.nchunks, p.cps);
-    p.nblocks = (int)(tiles * p.nsplit);
-    return p;
-}
-
 // f16 operands only on the vector path without tap folding (the 3-channel layers stay fp32)
 static bool wgrad_f16_ok(const hyres_wgrad_desc* d) {
-    const bool tapn = d->N <= 16 && d->ntaps > 1 && !d->square_q;
-    return d->f16_operands && !tapn && d->M % 4 == 0 && d->N % 4 == 0 && d->ldp % 4 == 0 && d->ldq % 4 == 0 &&
+    return d->f16_operands && !tap_folded(d) && d->M % 4 == 0 && d->N % 4 == 0 && d->ldp % 4 == 0 && d->ldq % 4 == 0 &&
            d->M >= 32 && d->N >= 32;
 }
 
@@ -2299,25 +2217,6 @@ static hyres_wgrad_desc wgrad_swapped(const hyres_wgrad_desc* d) {
     e.sm = d->sn; e.sn = d->sm;
     e.io_f16 = ((d->io_f16 & 1) << 1) | ((d->io_f16 >> 1) & 1);
     return e;
-}
-
-// fp16 operands (desc.io_f16) the chosen kernel reads natively: the f16 MFMA kernels either or both (AMP training:
-// the saved activation and, with fp16 activation gradients, the gradient), the thin kernel a fp16 P; every other
-// fp16 operand is converted into fp32 scratch before the launch (hyres_wgrad_workspace_bytes reserves it)
-static int wgrad_native_io(const hyres_wgrad_desc* d, bool thin) {
-    const int io = d->io_f16 & 3;
-    if (!io) return 0;
-    if (wgrad_f16_ok(d)) return io;
-    if (thin) return io & 1;
-    return 0;
-}
-
-static long long wgrad_cvt_floats(const hyres_wgrad_desc* d, int native) {
-    const int cvt = (d->io_f16 & 3) & ~native;
-    long long n = 0;
-    if (cvt & 1) n += (long long)d->B * d->Hq * d->Wq * d->M + 8;  // + 16-byte alignment slack
-    if (cvt & 2) n += (long long)d->B * d->Hqq * d->Wqq * d->N + 8;
-    return n;
 }
 
 // fp16 [P][C] (pixel stride ld) -> contiguous fp32 [P][C]
@@ -2368,73 +2267,237 @@ static bool thin_plan(const hyres_wgrad_desc* d, ThinPlan* tp) {
     return true;
 }
 
-static void launch_thin(const WgradArgs& a, const ThinPlan& p, bool ph, hipStream_t st) {
-    const dim3 grid(p.nblk, p.ngroups);
-    auto go = [&](auto mw, auto nc, auto tg) {
-        constexpr int MW_ = decltype(mw)::value, NC_ = decltype(nc)::value, TG_ = decltype(tg)::value;
-        if (p.sq == 1) {
-            if (ph) hipLaunchKernelGGL((wgrad_thin_kernel<MW_, NC_, TG_, 1, true>), grid, dim3(256), 0, st, a, p.rpb,
-                                       p.dhmin, p.dwmin, p.nrow, p.ncol, p.win);
-            else hipLaunchKernelGGL((wgrad_thin_kernel<MW_, NC_, TG_, 1>), grid, dim3(256), 0, st, a, p.rpb, p.dhmin,
-                                    p.dwmin, p.nrow, p.ncol, p.win);
-        } else {
-            if (ph) hipLaunchKernelGGL((wgrad_thin_kernel<MW_, NC_, TG_, 2, true>), grid, dim3(256), 0, st, a, p.rpb,
-                                       p.dhmin, p.dwmin, p.nrow, p.ncol, p.win);
-            else hipLaunchKernelGGL((wgrad_thin_kernel<MW_, NC_, TG_, 2>), grid, dim3(256), 0, st, a, p.rpb, p.dhmin,
-                                    p.dwmin, p.nrow, p.ncol, p.win);
-        }
-    };
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    using I4 = std::integral_constant<int, 4>;
-    using I9 = std::integral_constant<int, 9>;
-    using I13 = std::integral_constant<int, 13>;
-    using I25 = std::integral_constant<int, 25>;
-    if (p.mw == 1) {
-        if (p.nc == 3) { if (p.tg == 9) go(I1{}, I3{}, I9{}); else go(I1{}, I3{}, I25{}); }
-        else { if (p.tg == 9) go(I1{}, I4{}, I9{}); else go(I1{}, I4{}, I25{}); }
-    } else {
-        if (p.nc == 3) { if (p.tg == 9) go(I2{}, I3{}, I9{}); else go(I2{}, I3{}, I13{}); }
-        else { if (p.tg == 9) go(I2{}, I4{}, I9{}); else go(I2{}, I4{}, I13{}); }
+struct WgradRoute {
+    bool swap;           // computed transposed (wgrad_swap): P and Q trade places
+    hyres_wgrad_desc d;  // what the kernel runs on: swapped, its converted operands contiguous fp32
+    WgradFamily family;
+    bool f16, halo;                 // an f16-MFMA / halo-staged kernel: the plan assumed it, so it needs vp && vq
+    bool plain;                     // plain_1x1(d): ONE*, and F16's ONE flag
+    int TM, TN, WM, WN, NT;         // tile shape (GENERIC, F16, ONE*); NT = taps per block, the halo kernels' too
+    int KR, KW, SQ, DIL, hdh, hdw;  // HALO*: tap rows x columns per block, Q stride, tap spacing, first tap's (dh, dw)
+    ThinPlan thin;                  // THIN
+    int G;                          // ONE: 4-wave groups per block
+    int io, cvt;                    // fp16 operands (desc.io_f16 bits) read natively / converted to fp32 scratch first
+    bool vp, vq, sqr;               // float4 loads of P / Q, squared Q (GENERIC's template flags)
+    // the split plan (THIN: nsplit = its row blocks, one slab row each; the tiled fields are not read by that kernel)
+    int nsplit, cps, nchunks, mtiles, ntiles, ngroups, tapn, nblocks;
+    dim3 grid, block;
+    int lanes;  // of the split reduce
+    // workspace layout in floats: the slab at 0, the [nsplit][M] bias partials (swapped: the colsum scratch), the fp32
+    // copies of P and Q; total reserves both copies unless the f16 kernels read them (the thin kernel's fp16 P too)
+    long long bias_off, cvtp_off, cvtq_off, total;
+};
+
+static WgradRoute wgrad_route(const hyres_wgrad_desc* d0, const WgradFacts& f) {
+    WgradRoute r{};
+    r.swap = wgrad_swap(d0);
+    const hyres_wgrad_desc e = r.swap ? wgrad_swapped(d0) : *d0;
+    const hyres_wgrad_desc* d = &e;
+    const bool p16 = r.swap ? f.q16 : f.p16, q16 = r.swap ? f.p16 : f.q16;
+    const bool bf6 = f32_gemm_bf6();
+    auto fits32 = [](long long bytes) { return bytes < 0x7FFFFFF0LL; };
+    const long long Pp = (long long)d->B * d->Hq * d->Wq, Pq = (long long)d->B * d->Hqq * d->Wqq;  // P / Q pixels
+    r.plain = plain_1x1(d);
+    r.sqr = d->square_q != 0;
+    int hk = 0, hdil = 1;
+    r.halo = halo_ok(d, &hk, &hdil);  // fp32 or (AMP) f16 halo kernel: 32-pixel chunks either way
+    const bool f16 = wgrad_f16_ok(d);
+    const int kt = (f16 && !r.halo) ? KTH : KT;
+    const bool thin = thin_plan(d, &r.thin) && p16;
+
+    // tile shape
+    r.TM = r.TN = 1; r.WM = r.WN = 2; r.NT = 1;
+    r.tapn = tap_folded(d);
+    const int ncols = r.tapn ? d->ntaps * d->N : d->N;
+    if (r.halo) {
+        // 64 x 64. 3x3: one kernel row of 3 taps per block, or all 9 taps per block (one 3-row halo per chunk) — rows
+        // of 3 give 3x the tiles, so a third of the pixel splits and of the split slab for the same grid. Default: rows
+        // for dilation 1 (AMP step 21.56 -> 21.34 ms, fp32 42.82 -> 42.68 ms over 3 alternating repeats each;
+        // 128^2 fp32 kernel 235 -> 208 us), all 9 taps for the dilated 3x3s (256^2: 678 vs 797 us fp32, 152 vs 219 us
+        // f16: their halo rows are 2 apart, so a row group re-stages most of the chunk; profiles/r3r_rows_ab.txt,
+        // r3y_rows_fp32_ab.txt)
+        r.NT = hk == 5 ? 5 : hdil == 2 ? 9 : 3;
+        r.KR = r.NT == 9 ? 3 : 1; r.KW = hk; r.SQ = hk == 5 ? d->sq : 1; r.DIL = hdil;
+        r.hdh = d->dh[0]; r.hdw = d->dw[0];
+    } else if (r.tapn) {
+        if (ncols <= 32) { r.WM = 4; r.WN = 1; }
+    } else if (d->M >= 128 && d->N >= 128) { r.TM = r.TN = 2; }
+    else if (d->M >= 128 && d->N >= 64 && d->ntaps == 1) { r.TM = 2; }
+    else if (d->M <= 32) { r.WM = 1; r.WN = 4; }
+    else if (d->N <= 32) { r.WM = 4; r.WN = 1; }
+    else {
+        // fp32: group 9 / 5 taps per block (operand reuse); f16: one tap per block column group (measured
+        // faster on every f16 geometry of the step: the f16 main loop is short, more blocks hide it better)
+        r.NT = (d->ntaps % 9 == 0) ? 9 : (d->ntaps % 5 == 0) ? 5 : 1;
+        if (kt == KTH || g_tune[5] == 1) r.NT = 1;
     }
+    r.mtiles = ceil_div(d->M, 32 * r.TM * r.WM); r.ntiles = ceil_div(ncols, 32 * r.TN * r.WN);
+    r.ngroups = r.tapn ? 1 : ceil_div(d->ntaps, r.NT);
+    r.nchunks = ceil_div(Pp, kt);
+
+    // split plan
+    const long long tiles = (long long)r.mtiles * r.ntiles * r.ngroups;
+    // ~2048 blocks (swept on MI355X: 1024 -> 2048 is -0.6 % step time; fewer splits hurt), >= 8 chunks
+    // (256 pixels; f16: 4 chunks of 64) per split, <= 512 splits (hyres_conv_tuning keys 3, 4, 6 override them for
+    // sweeps). Small grids (<= 16384 pixels, the 32^2 region at
+    // bs 16): ~4096 blocks, fp32 multi-tap splits down to 4 chunks. The split count is capped so that the partial
+    // slab stays <= 16 M floats (64 MB): for the wide 1x1 layers (M x N ~ 0.5 M) the slab write + reduce
+    // otherwise costs more than the parallelism buys (scripts/tile_sweep.py --wgrad)
+    const bool small = Pp <= 16384;
+    const int tb = g_tune[3] > 0 ? g_tune[3] : (small ? 4096 : 2048);
+    const int mc0 = g_tune[4] > 0 ? g_tune[4] : ((small && kt == KT && d->ntaps > 1) ? 4 : 8);
+    const int mc = std::max(1, mc0 * KT / kt);
+    // <= 256 splits (<= 64 on the small grids): past that the split slab's write + reduce costs more than the
+    // extra blocks buy — step 32.79 -> 32.54 ms, AMP 19.10 -> 18.76 ms against 512 everywhere (isolated, kernel +
+    // reduce: 128^2 3x3 64->64 143 -> 137 us, 32^2 3x3 96->96 51.6 -> 43.4 us; one exception measured, 256^2 1x1
+    // 64->64 132 -> 160 us, but 512 splits for the 1x1s only gave no step gain; profiles/r5z_wgrad_split_ab.txt)
+    const int ms = g_tune[6] > 0 ? g_tune[6] : (small ? 64 : 256);
+    const long long slab_cap = std::max<long long>(4, (16LL << 20) / ((long long)d->ntaps * d->M * d->N));
+    const long long want = std::min<long long>(std::max<long long>(1, (tb + tiles - 1) / tiles), slab_cap);
+    const long long maxsplit = std::max<long long>(1, r.nchunks / mc);
+    r.nsplit = (int)std::min<long long>(std::min<long long>(want, maxsplit), ms);
+    if (r.halo) {
+        // whole rounds only: the halo kernel runs 2 blocks per CU (3 for 5x5 stride 1); a partial last round
+        // of long split-K blocks costs as much as a full one, so drop it (e.g. 800 -> 500 blocks)
+        // (the bf16x6 kernel: 1 block per CU when it stages all 9 taps' halo, 158 KB of LDS)
+        const bool b6_9 = bf6 && !f16 && r.NT == 9;
+        const long long cap = (long long)num_cus() * (b6_9 ? 1 : (hk == 5 && d->sq == 1) ? 3 : 2);
+        if (tiles * r.nsplit > cap) r.nsplit = (int)std::max<long long>(1, (tiles * r.nsplit / cap) * cap / tiles);
+        // and fill a partial single round when that grows the slab by <= 25 % (128^2 3x3: 455 -> 512)
+        else if (cap / tiles <= maxsplit && 4 * (cap / tiles) <= 5LL * r.nsplit) r.nsplit = (int)(cap / tiles);
+    }
+    // plain 1x1 fp32 gradients (wgrad1x1_kernel) outside the small grids: 2 groups of 4 waves per block share
+    // one split's pixels, so the same waves write half the slab. Isolated 128^2 64<->128: 65 -> 62 us; on the 32^2
+    // grids it lost (24.6 -> 30.5 us: half the blocks). (Two groups per block for the halo kernels — half their
+    // split slab — won isolated but lost in the live step, 40.0 -> 41.1 ms: the 146 KB block keeps the concurrent
+    // branches' blocks off its CU; profiles/r3o_halo_groups.txt.) The plan does not look at the alignment: a
+    // misaligned operand sends the halved split to wgrad_kernel.
+    r.G = 1;
+    if (r.plain && !small && kt == KT && !bf6 && r.nsplit >= 2) {
+        r.G = 2;
+        r.nsplit = (r.nsplit + 1) / 2;
+    }
+    r.cps = ceil_div(r.nchunks, r.nsplit);
+    r.nsplit = ceil_div(r.nchunks, r.cps);
+    r.nblocks = (int)(tiles * r.nsplit);
+    if (thin) r.nsplit = r.thin.nblk;  // one slab row per thin block
+
+    // fp16 operands (desc.io_f16) the kernel reads natively: the f16 MFMA kernels either or both (AMP training: the
+    // saved activation and, with fp16 activation gradients, the gradient), the thin kernel a fp16 P; every other fp16
+    // operand gets a contiguous fp32 copy after the slab and the bias partials
+    const int io = d->io_f16 & 3;
+    r.io = f16 ? io : thin ? io & 1 : 0;
+    r.cvt = io & ~r.io;
+    auto al4 = [](long long n) { return (n + 3) & ~3LL; };
+    const long long slab = (long long)r.nsplit * d->ntaps * (long long)d->M * d->N;
+    const long long bias = (r.swap ? hyres_colsum_workspace_bytes(d->B * d->Hq * d->Wq, d->N) / 4
+                                   : (long long)r.nsplit * d->M) + 4;
+    r.bias_off = slab;
+    r.cvtp_off = al4(slab + bias);
+    r.cvtq_off = r.cvtp_off + ((r.cvt & 1) ? al4(Pp * d->M) : 0);
+    const int rsv = f16 ? 0 : io;  // + 8: 16-byte alignment slack
+    r.total = slab + bias + ((rsv & 1) ? Pp * d->M + 8 : 0) + ((rsv & 2) ? Pq * d->N + 8 : 0);
+    r.d = e;
+    if (r.cvt & 1) r.d.ldp = d->M;
+    if (r.cvt & 2) r.d.ldq = d->N;
+    r.d.io_f16 = r.io;
+    r.vp = (d->M % 4 == 0) && (r.d.ldp % 4 == 0) && ((r.cvt & 1) ? f.ws16 : p16);
+    r.vq = !r.tapn && (d->N % 4 == 0) && (r.d.ldq % 4 == 0) && ((r.cvt & 2) ? f.ws16 : q16);
+
+    // the family. f16 is read off the launch desc: it differs from the plan's only when a conversion has just made a
+    // fp16 operand's stride a multiple of 4
+    r.f16 = wgrad_f16_ok(&r.d);
+    if (!thin && !r.halo && !r.f16 && r.plain && r.vp && r.vq)
+        // bf16x6 products (the plan keeps one 4-wave group per block for them), loads two chunks ahead (key 15 = 2)
+        r.family = !bf6 ? WgradFamily::ONE
+                   : (g_tune[15] == 2 && fits32(Pp * std::max(r.d.ldp, r.d.ldq) * 4)) ? WgradFamily::ONE_B6_PF2
+                                                                                     : WgradFamily::ONE_B6;
+    else if (thin) r.family = WgradFamily::THIN;
+    else if (r.halo && r.f16) r.family = WgradFamily::HALO_F16;
+    else if (r.halo && bf6)  // fp32 operands (fp16 ones are converted), bf16x6 products; key 16 = 2: two chunks ahead
+        r.family = (g_tune[16] == 2 && (r.NT == 3 || (r.NT == 5 && g_tune[22] != 0)) && fits32(Pq * r.d.ldq * 4) &&
+                    fits32(Pp * r.d.ldp * 4)) ? WgradFamily::HALO_B6_PF2 : WgradFamily::HALO_B6;
+    else if (r.halo) r.family = WgradFamily::HALO;
+    else r.family = r.f16 ? WgradFamily::F16 : WgradFamily::GENERIC;
+
+    const bool is_thin = r.family == WgradFamily::THIN;
+    r.grid = is_thin ? dim3(r.thin.nblk, r.thin.ngroups) : dim3(ceil_div(r.nblocks, 8) * 8);
+    r.block = dim3(r.family == WgradFamily::ONE ? 256 * r.G : 256);
+    r.lanes = reduce_lx((long long)d->ntaps * d->M * d->N, r.nsplit);
+    return r;
+}
+
+// The shape cascades: a runtime shape -> std::integral_constants for a generic lambda to instantiate its kernel with
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+template <typename F>
+static void with_tile(const WgradRoute& r, F&& f) {  // f(TM, TN, WM, WN, NT)
+    if (r.TM == 2 && r.TN == 2) f(IC<2>{}, IC<2>{}, IC<2>{}, IC<2>{}, IC<1>{});
+    else if (r.TM == 2) f(IC<2>{}, IC<1>{}, IC<2>{}, IC<2>{}, IC<1>{});
+    else if (r.WM == 1) f(IC<1>{}, IC<1>{}, IC<1>{}, IC<4>{}, IC<1>{});
+    else if (r.WN == 1) f(IC<1>{}, IC<1>{}, IC<4>{}, IC<1>{}, IC<1>{});
+    else if (r.NT == 9) f(IC<1>{}, IC<1>{}, IC<2>{}, IC<2>{}, IC<9>{});
+    else if (r.NT == 5) f(IC<1>{}, IC<1>{}, IC<2>{}, IC<2>{}, IC<5>{});
+    else f(IC<1>{}, IC<1>{}, IC<2>{}, IC<2>{}, IC<1>{});
+}
+
+template <typename F>
+static void with_halo(const WgradRoute& r, F&& f) {  // f(KR, KW, SQ, DIL)
+    if (r.KW == 3 && r.KR == 1 && r.DIL == 2) f(IC<1>{}, IC<3>{}, IC<1>{}, IC<2>{});
+    else if (r.KW == 3 && r.KR == 1) f(IC<1>{}, IC<3>{}, IC<1>{}, IC<1>{});
+    else if (r.KW == 3 && r.DIL == 2) f(IC<3>{}, IC<3>{}, IC<1>{}, IC<2>{});
+    else if (r.KW == 3) f(IC<3>{}, IC<3>{}, IC<1>{}, IC<1>{});
+    else if (r.SQ == 1) f(IC<1>{}, IC<5>{}, IC<1>{}, IC<1>{});  // 5x5 stride 1: 3 blocks per CU
+    else f(IC<1>{}, IC<5>{}, IC<2>{}, IC<1>{});
+}
+
+// wgrad_halo_bf6_pf2_kernel's MINB: the 5x5 stride 2 runs 1 block per CU
+constexpr int halo_pf2_minb(int kw, int sq) { return (kw == 5 && sq == 2) ? 1 : 2; }
+
+template <typename F>
+static void with_io(int io, F&& f) {  // f(IOH)
+    if (io == 1) f(IC<1>{});
+    else if (io == 2) f(IC<2>{});
+    else if (io == 3) f(IC<3>{});
+    else f(IC<0>{});
+}
+
+static void launch_thin(const WgradArgs& a, const WgradRoute& r, hipStream_t st) {
+    const ThinPlan& p = r.thin;
+    auto go = [&](auto mw, auto nc, auto tg, auto sq, auto ph) {  // ph: P fp16 in HBM
+        hipLaunchKernelGGL((wgrad_thin_kernel<mw(), nc(), tg(), sq(), ph() != 0>), r.grid, r.block, 0, st, a, p.rpb,
+                           p.dhmin, p.dwmin, p.nrow, p.ncol, p.win);
+    };
+    auto by_sq = [&](auto mw, auto nc, auto tg) {
+        if (p.sq == 1) { if (r.io & 1) go(mw, nc, tg, IC<1>{}, IC<1>{}); else go(mw, nc, tg, IC<1>{}, IC<0>{}); }
+        else { if (r.io & 1) go(mw, nc, tg, IC<2>{}, IC<1>{}); else go(mw, nc, tg, IC<2>{}, IC<0>{}); }
+    };
+    auto by_nc = [&](auto mw, auto tgmax) {  // tap groups of 9, or of the width's most (25 / 13)
+        if (p.nc == 3) { if (p.tg == 9) by_sq(mw, IC<3>{}, IC<9>{}); else by_sq(mw, IC<3>{}, tgmax); }
+        else { if (p.tg == 9) by_sq(mw, IC<4>{}, IC<9>{}); else by_sq(mw, IC<4>{}, tgmax); }
+    };
+    if (p.mw == 1) by_nc(IC<1>{}, IC<25>{});
+    else by_nc(IC<2>{}, IC<13>{});
 }
 
 template <int TM, int TN, int WM_, int WN_, int NT>
-static void launch_wgrad(const WgradArgs& a, bool vp, bool vq, bool sqr, dim3 grid, hipStream_t st) {
-    if (vp && vq && sqr) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, true, true, true>), grid, dim3(256), 0, st, a);
-    else if (vp && vq) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, true, true, false>), grid, dim3(256), 0, st, a);
-    else if (vp) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, true, false, false>), grid, dim3(256), 0, st, a);
-    else if (vq) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, false, true, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, false, false, false>), grid, dim3(256), 0, st, a);
+static void launch_wgrad(const WgradArgs& a, const WgradRoute& r, hipStream_t st) {
+    const dim3 grid = r.grid, blk = r.block;
+    if (r.vp && r.vq && r.sqr) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, true, true, true>), grid, blk, 0, st, a);
+    else if (r.vp && r.vq) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, true, true, false>), grid, blk, 0, st, a);
+    else if (r.vp) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, true, false, false>), grid, blk, 0, st, a);
+    else if (r.vq) hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, false, true, false>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((wgrad_kernel<TM, TN, WM_, WN_, NT, false, false, false>), grid, blk, 0, st, a);
 }
 
 }  // namespace hyres
 
 extern "C" {
 
-static long long wgrad_slab_floats(const hyres_wgrad_desc* e, const WgradPlan& p) {
-    return (long long)p.nsplit * e->ntaps * (long long)e->M * e->N;
-}
-
+// the larger of the thin and the tiled paths' needs: a thin desc takes the tiled path when its P is not 16-byte aligned
 long long hyres_wgrad_workspace_bytes(const hyres_wgrad_desc* d) {
-    const bool swap = wgrad_swap(d);
-    hyres_wgrad_desc e = swap ? wgrad_swapped(d) : *d;
-    WgradPlan p = wgrad_plan(&e);
-    // + the bias-gradient partials: [nsplit][M] in the kernel, or colsum partials when swapped
-    auto need = [&](const WgradPlan& q) {
-        const long long bias = swap ? hyres_colsum_workspace_bytes(d->B * d->Hq * d->Wq, d->M) / 4 + 4
-                                    : (long long)q.nsplit * e.M + 4;
-        return (wgrad_slab_floats(&e, q) + bias + wgrad_cvt_floats(&e, wgrad_native_io(&e, false))) * 4;
-    };
-    long long bytes = need(p);
-    ThinPlan tp;
-    if (thin_plan(&e, &tp)) {  // one slab row per thin block (the launch may still take the generic path
-        WgradPlan q = p;       // when P is not 16-byte aligned: cover both)
-        q.nsplit = tp.nblk;
-        bytes = std::max(bytes, need(q));
-    }
-    return bytes;
+    return 4 * std::max(wgrad_route(d, WgradFacts::ideal()).total, wgrad_route(d, WgradFacts{false, false, true}).total);
 }
 
 // Launch the weight-gradient GEMM (and, for the swapped small-M layers, the bias column sums) and describe the
@@ -2445,203 +2508,102 @@ static int wgrad_issue(const hyres_wgrad_desc* d0, const float* pp, const float*
     HY_REQUIRE(d0 && pp && qq && dst, HYRES_E_ARG, "wgrad: NULL");
     const long long need = hyres_wgrad_workspace_bytes(d0);
     HY_REQUIRE(ws && ws_bytes >= need, HYRES_E_WORKSPACE, "wgrad: workspace %lld < %lld", ws_bytes, need);
+    const WgradRoute r = wgrad_route(d0, WgradFacts{aligned16(pp), aligned16(qq), aligned16(ws)});
+    const hyres_wgrad_desc* d = &r.d;
     const float* p_orig = pp;
-    const bool swap = wgrad_swap(d0);
-    hyres_wgrad_desc dd = swap ? wgrad_swapped(d0) : *d0;
-    const hyres_wgrad_desc* d = &dd;
-    if (swap) std::swap(pp, qq);
-    WgradPlan p = wgrad_plan(d);
-    ThinPlan tp;
-    const bool thin = thin_plan(d, &tp) && aligned16(pp);
-    if (thin) p.nsplit = tp.nblk;
-    float* bias_ws = (float*)ws + wgrad_slab_floats(d, p);
-    int io = dd.io_f16 & 3;
-    {
-        // fp16 operands the chosen kernel cannot read: contiguous fp32 copies after the slab and bias partials
-        // (the plan does not depend on the operand dtype or pixel stride beyond the checks below)
-        const int native = wgrad_native_io(d, thin);
-        const int cvt = io & ~native;
-        auto al4 = [](long long n) { return (n + 3) & ~3LL; };
-        float* cws = (float*)ws + al4(wgrad_slab_floats(d, p) + (swap ? hyres_colsum_workspace_bytes(d0->B * d0->Hq * d0->Wq,
-                                                                                                      d0->M) / 4 + 4
-                                                                      : (long long)p.nsplit * d->M + 4));
-        hipStream_t st0 = as_stream(s);
-        if (cvt & 1) {
-            const long long P = (long long)dd.B * dd.Hq * dd.Wq;
-            hipLaunchKernelGGL(half_to_float_2d_kernel, dim3((unsigned)std::min<long long>((P * dd.M + 255) / 256, 8192)),
-                               dim3(256), 0, st0, (const _Float16*)pp, dd.ldp, cws, P, dd.M);
-            pp = cws; dd.ldp = dd.M; cws += al4(P * dd.M);
-        }
-        if (cvt & 2) {
-            const long long P = (long long)dd.B * dd.Hqq * dd.Wqq;
-            hipLaunchKernelGGL(half_to_float_2d_kernel, dim3((unsigned)std::min<long long>((P * dd.N + 255) / 256, 8192)),
-                               dim3(256), 0, st0, (const _Float16*)qq, dd.ldq, cws, P, dd.N);
-            qq = cws; dd.ldq = dd.N;
-        }
-        if (cvt) {
-            int rc0 = HY_LAUNCH_CHECK("half_to_float_2d");
-            if (rc0) return rc0;
-        }
-        io &= native;
-        dd.io_f16 = io;
-    }
-    const bool vp = (d->M % 4 == 0) && (d->ldp % 4 == 0) && aligned16(pp);
-    const bool vq = !p.tapn && (d->N % 4 == 0) && (d->ldq % 4 == 0) && aligned16(qq);
-    HY_REQUIRE(!d->square_q || (vp && vq), HYRES_E_SHAPE, "wgrad: square_q needs the vector path");
-    // the plan (chunk size, split count, workspace) assumed the f16 kernel: its operands must be aligned
-    HY_REQUIRE(!wgrad_f16_ok(d) || (vp && vq), HYRES_E_ALIGN, "wgrad(f16): P/Q must be 16-byte aligned");
-    HY_REQUIRE(!p.halo || (vp && vq), HYRES_E_ALIGN, "wgrad(halo): P/Q must be 16-byte aligned");
-    WgradArgs a;
-    a.d = *d; a.p = pp; a.q = qq; a.slab = (float*)ws; a.chunks_per_split = p.cps; a.nchunks = p.nchunks;
-    a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.ngroups = p.ngroups; a.nblocks = p.nblocks; a.tapn = p.tapn;
-    a.bias_slab = (dbias && !swap) ? bias_ws : nullptr;
-    dim3 grid(ceil_div(p.nblocks, 8) * 8);
+    if (r.swap) std::swap(pp, qq);
+    float* const wsf = (float*)ws;
+    float* const bias_ws = wsf + r.bias_off;
     hipStream_t st = as_stream(s);
-    const bool sqr = d->square_q != 0;
-    const bool one = !thin && !p.halo && !wgrad_f16_ok(d) && !sqr && !p.tapn && vp && vq &&
-                     d->ntaps == 1 && d->dh[0] == 0 && d->dw[0] == 0 && d->sq == 1 && d->Hqq == d->Hq &&
-                     d->Wqq == d->Wq && p.ngroups == 1;
-    const bool pf2 = g_tune[15] == 2 && (long long)d->B * d->Hq * d->Wq * std::max(d->ldp, d->ldq) * 4 < 0x7FFFFFF0LL;
-    if (one && f32_gemm_bf6() && pf2) {  // loads two chunks ahead (key 15 = 2)
-        if (p.TMc == 2 && p.TNc == 2) hipLaunchKernelGGL((wgrad1x1_bf6_pf2_kernel<2, 2, 2, 2>), grid, dim3(256), 0, st, a);
-        else if (p.TMc == 2) hipLaunchKernelGGL((wgrad1x1_bf6_pf2_kernel<2, 1, 2, 2>), grid, dim3(256), 0, st, a);
-        else if (p.WMc == 1) hipLaunchKernelGGL((wgrad1x1_bf6_pf2_kernel<1, 1, 1, 4>), grid, dim3(256), 0, st, a);
-        else if (p.WNc == 1) hipLaunchKernelGGL((wgrad1x1_bf6_pf2_kernel<1, 1, 4, 1>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wgrad1x1_bf6_pf2_kernel<1, 1, 2, 2>), grid, dim3(256), 0, st, a);
-    } else if (one && f32_gemm_bf6()) {  // bf16x6 products (the plan keeps one 4-wave group per block for it)
-        if (p.TMc == 2 && p.TNc == 2) hipLaunchKernelGGL((wgrad1x1_bf6_kernel<2, 2, 2, 2>), grid, dim3(256), 0, st, a);
-        else if (p.TMc == 2) hipLaunchKernelGGL((wgrad1x1_bf6_kernel<2, 1, 2, 2>), grid, dim3(256), 0, st, a);
-        else if (p.WMc == 1) hipLaunchKernelGGL((wgrad1x1_bf6_kernel<1, 1, 1, 4>), grid, dim3(256), 0, st, a);
-        else if (p.WNc == 1) hipLaunchKernelGGL((wgrad1x1_bf6_kernel<1, 1, 4, 1>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wgrad1x1_bf6_kernel<1, 1, 2, 2>), grid, dim3(256), 0, st, a);
-    } else if (one) {
-        auto w1 = [&](auto gc) {
-            constexpr int G_ = decltype(gc)::value;
-            const dim3 blk(256 * G_);
-            if (p.TMc == 2 && p.TNc == 2) hipLaunchKernelGGL((wgrad1x1_kernel<2, 2, 2, 2, G_>), grid, blk, 0, st, a);
-            else if (p.TMc == 2) hipLaunchKernelGGL((wgrad1x1_kernel<2, 1, 2, 2, G_>), grid, blk, 0, st, a);
-            else if (p.WMc == 1) hipLaunchKernelGGL((wgrad1x1_kernel<1, 1, 1, 4, G_>), grid, blk, 0, st, a);
-            else if (p.WNc == 1) hipLaunchKernelGGL((wgrad1x1_kernel<1, 1, 4, 1, G_>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((wgrad1x1_kernel<1, 1, 2, 2, G_>), grid, blk, 0, st, a);
-        };
-        if (p.g1x1 == 2) w1(std::integral_constant<int, 2>{});
-        else w1(std::integral_constant<int, 1>{});
-    } else if (thin) {
-        launch_thin(a, tp, (io & 1) != 0, st);
-    } else if (p.halo && wgrad_f16_ok(d)) {
-        auto halo16 = [&](auto ioc, auto gc) {
-            constexpr int IO_ = decltype(ioc)::value, G_ = decltype(gc)::value;
-            const dim3 blk(256 * G_);
-            if (p.hk == 3 && p.NT == 3 && p.hdil == 2)
-                hipLaunchKernelGGL((wgrad_halo_f16_kernel<1, 3, 1, 2, IO_, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (p.hk == 3 && p.NT == 3)
-                hipLaunchKernelGGL((wgrad_halo_f16_kernel<1, 3, 1, 1, IO_, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (p.hk == 3 && p.hdil == 2)
-                hipLaunchKernelGGL((wgrad_halo_f16_kernel<3, 3, 1, 2, IO_, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (p.hk == 3)
-                hipLaunchKernelGGL((wgrad_halo_f16_kernel<3, 3, 1, 1, IO_, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (d->sq == 1)  // 5x5 stride 1: one group (3 blocks per CU)
-                hipLaunchKernelGGL((wgrad_halo_f16_kernel<1, 5, 1, 1, IO_>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-            else hipLaunchKernelGGL((wgrad_halo_f16_kernel<1, 5, 2, 1, IO_, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-        };
-        auto halo16g = [&](auto ioc) { halo16(ioc, std::integral_constant<int, 1>{}); };
-        if (io == 1) halo16g(std::integral_constant<int, 1>{});
-        else if (io == 2) halo16g(std::integral_constant<int, 2>{});
-        else if (io == 3) halo16g(std::integral_constant<int, 3>{});
-        else halo16g(std::integral_constant<int, 0>{});
-    } else if (p.halo && f32_gemm_bf6() && g_tune[16] == 2 && (p.NT == 3 || (p.NT == 5 && g_tune[22] != 0)) &&
-               (long long)d->B * d->Hqq * d->Wqq * d->ldq * 4 < 0x7FFFFFF0LL &&
-               (long long)d->B * d->Hq * d->Wq * d->ldp * 4 < 0x7FFFFFF0LL) {  // loads two chunks ahead (key 16 = 2)
-        if (p.hk == 3 && p.hdil == 2)
-            hipLaunchKernelGGL((wgrad_halo_bf6_pf2_kernel<3, 1, 2>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else if (p.hk == 3)
-            hipLaunchKernelGGL((wgrad_halo_bf6_pf2_kernel<3, 1, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else if (d->sq == 1)
-            hipLaunchKernelGGL((wgrad_halo_bf6_pf2_kernel<5, 1, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else hipLaunchKernelGGL((wgrad_halo_bf6_pf2_kernel<5, 2, 1, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-    } else if (p.halo && f32_gemm_bf6()) {  // fp32 operands (fp16 ones were converted above), bf16x6 products
-        if (p.hk == 3 && p.NT == 3 && p.hdil == 2)
-            hipLaunchKernelGGL((wgrad_halo_bf6_kernel<1, 3, 1, 2>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else if (p.hk == 3 && p.NT == 3)
-            hipLaunchKernelGGL((wgrad_halo_bf6_kernel<1, 3, 1, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else if (p.hk == 3 && p.hdil == 2)
-            hipLaunchKernelGGL((wgrad_halo_bf6_kernel<3, 3, 1, 2>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else if (p.hk == 3)
-            hipLaunchKernelGGL((wgrad_halo_bf6_kernel<3, 3, 1, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else if (d->sq == 1)
-            hipLaunchKernelGGL((wgrad_halo_bf6_kernel<1, 5, 1, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-        else hipLaunchKernelGGL((wgrad_halo_bf6_kernel<1, 5, 2, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-    } else if (p.halo) {
-        auto halo32 = [&](auto gc) {
-            constexpr int G_ = decltype(gc)::value;
-            const dim3 blk(256 * G_);
-            if (p.hk == 3 && p.NT == 3 && p.hdil == 2)
-                hipLaunchKernelGGL((wgrad_halo_kernel<1, 3, 1, 2, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (p.hk == 3 && p.NT == 3)
-                hipLaunchKernelGGL((wgrad_halo_kernel<1, 3, 1, 1, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (p.hk == 3 && p.hdil == 2)
-                hipLaunchKernelGGL((wgrad_halo_kernel<3, 3, 1, 2, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (p.hk == 3)
-                hipLaunchKernelGGL((wgrad_halo_kernel<3, 3, 1, 1, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-            else if (d->sq == 1)  // 5x5 stride 1: one group (3 blocks per CU)
-                hipLaunchKernelGGL((wgrad_halo_kernel<1, 5, 1>), grid, dim3(256), 0, st, a, p.hdh, p.hdw);
-            else hipLaunchKernelGGL((wgrad_halo_kernel<1, 5, 2, 1, G_>), grid, blk, 0, st, a, p.hdh, p.hdw);
-        };
-        halo32(std::integral_constant<int, 1>{});
-    } else if (wgrad_f16_ok(d)) {
-        const bool one16 = !sqr && d->ntaps == 1 && d->dh[0] == 0 && d->dw[0] == 0 && d->sq == 1 &&
-                           d->Hqq == d->Hq && d->Wqq == d->Wq && p.ngroups == 1;
-        auto f16io = [&](auto tm, auto tn, auto wm_, auto wn_, auto ntc, auto ioc) {
-            constexpr int TM_ = decltype(tm)::value, TN_ = decltype(tn)::value;
-            constexpr int WM2 = decltype(wm_)::value, WN2 = decltype(wn_)::value, NT_ = decltype(ntc)::value;
-            constexpr int IO_ = decltype(ioc)::value;
-            if (sqr) {
-                // GDN: Q = x (fp16 in AMP training), P = the norm gradient (fp16 with AMP fp16 gradients)
-                hipLaunchKernelGGL((wgrad_f16_kernel<TM_, TN_, WM2, WN2, NT_, true, false, IO_>), grid, dim3(256), 0, st,
-                                   a);
-            } else if (NT_ == 1 && one16) {
-                hipLaunchKernelGGL((wgrad_f16_kernel<TM_, TN_, WM2, WN2, 1, false, true, IO_>), grid, dim3(256), 0, st,
-                                   a);
-            } else {
-                hipLaunchKernelGGL((wgrad_f16_kernel<TM_, TN_, WM2, WN2, NT_, false, false, IO_>), grid, dim3(256), 0,
-                                   st, a);
-            }
-        };
-        auto f16 = [&](auto tm, auto tn, auto wm_, auto wn_, auto ntc) {
-            if (io == 1) f16io(tm, tn, wm_, wn_, ntc, std::integral_constant<int, 1>{});
-            else if (io == 2) f16io(tm, tn, wm_, wn_, ntc, std::integral_constant<int, 2>{});
-            else if (io == 3) f16io(tm, tn, wm_, wn_, ntc, std::integral_constant<int, 3>{});
-            else f16io(tm, tn, wm_, wn_, ntc, std::integral_constant<int, 0>{});
-        };
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        using I4 = std::integral_constant<int, 4>;
-        if (p.TMc == 2 && p.TNc == 2) f16(I2{}, I2{}, I2{}, I2{}, I1{});
-        else if (p.TMc == 2) f16(I2{}, I1{}, I2{}, I2{}, I1{});
-        else if (p.WMc == 1) f16(I1{}, I1{}, I1{}, I4{}, I1{});
-        else if (p.WNc == 1) f16(I1{}, I1{}, I4{}, I1{}, I1{});
-        else if (p.NT == 9) f16(I1{}, I1{}, I2{}, I2{}, std::integral_constant<int, 9>{});
-        else if (p.NT == 5) f16(I1{}, I1{}, I2{}, I2{}, std::integral_constant<int, 5>{});
-        else f16(I1{}, I1{}, I2{}, I2{}, I1{});
-    } else if (p.TMc == 2 && p.TNc == 2) launch_wgrad<2, 2, 2, 2, 1>(a, vp, vq, sqr, grid, st);
-    else if (p.TMc == 2) launch_wgrad<2, 1, 2, 2, 1>(a, vp, vq, sqr, grid, st);
-    else if (p.WMc == 1) launch_wgrad<1, 1, 1, 4, 1>(a, vp, vq, sqr, grid, st);
-    else if (p.WNc == 1) launch_wgrad<1, 1, 4, 1, 1>(a, vp, vq, sqr, grid, st);
-    else if (p.NT == 9) launch_wgrad<1, 1, 2, 2, 9>(a, vp, vq, sqr, grid, st);
-    else if (p.NT == 5) launch_wgrad<1, 1, 2, 2, 5>(a, vp, vq, sqr, grid, st);
-    else launch_wgrad<1, 1, 2, 2, 1>(a, vp, vq, sqr, grid, st);
+    auto to_f32 = [&](const float*& x, int ld, long long P, int C, long long off) {
+        hipLaunchKernelGGL(half_to_float_2d_kernel, dim3((unsigned)std::min<long long>((P * C + 255) / 256, 8192)),
+                           dim3(256), 0, st, (const _Float16*)x, ld, wsf + off, P, C);
+        x = wsf + off;
+    };
+    if (r.cvt & 1) to_f32(pp, r.swap ? d0->ldq : d0->ldp, (long long)d->B * d->Hq * d->Wq, d->M, r.cvtp_off);
+    if (r.cvt & 2) to_f32(qq, r.swap ? d0->ldp : d0->ldq, (long long)d->B * d->Hqq * d->Wqq, d->N, r.cvtq_off);
+    if (r.cvt) {
+        int rc0 = HY_LAUNCH_CHECK("half_to_float_2d");
+        if (rc0) return rc0;
+    }
+    const bool vec = r.vp && r.vq;
+    HY_REQUIRE(!r.sqr || vec, HYRES_E_SHAPE, "wgrad: square_q needs the vector path");
+    // the plan (chunk size, split count, workspace) assumed the f16 kernel: its operands must be aligned
+    HY_REQUIRE(!r.f16 || vec, HYRES_E_ALIGN, "wgrad(f16): P/Q must be 16-byte aligned");
+    HY_REQUIRE(!r.halo || vec, HYRES_E_ALIGN, "wgrad(halo): P/Q must be 16-byte aligned");
+    WgradArgs a;
+    a.d = *d; a.p = pp; a.q = qq; a.slab = wsf; a.chunks_per_split = r.cps; a.nchunks = r.nchunks;
+    a.mtiles = r.mtiles; a.ntiles = r.ntiles; a.ngroups = r.ngroups; a.nblocks = r.nblocks; a.tapn = r.tapn;
+    a.bias_slab = (dbias && !r.swap) ? bias_ws : nullptr;
+    const dim3 grid = r.grid, blk = r.block;
+    switch (r.family) {
+        case WgradFamily::ONE_B6_PF2:
+            with_tile(r, [&](auto tm, auto tn, auto wm, auto wn, auto) {
+                hipLaunchKernelGGL((wgrad1x1_bf6_pf2_kernel<tm(), tn(), wm(), wn()>), grid, blk, 0, st, a);
+            });
+            break;
+        case WgradFamily::ONE_B6:
+            with_tile(r, [&](auto tm, auto tn, auto wm, auto wn, auto) {
+                hipLaunchKernelGGL((wgrad1x1_bf6_kernel<tm(), tn(), wm(), wn()>), grid, blk, 0, st, a);
+            });
+            break;
+        case WgradFamily::ONE:
+            with_tile(r, [&](auto tm, auto tn, auto wm, auto wn, auto) {
+                if (r.G == 2) hipLaunchKernelGGL((wgrad1x1_kernel<tm(), tn(), wm(), wn(), 2>), grid, blk, 0, st, a);
+                else hipLaunchKernelGGL((wgrad1x1_kernel<tm(), tn(), wm(), wn(), 1>), grid, blk, 0, st, a);
+            });
+            break;
+        case WgradFamily::THIN: launch_thin(a, r, st); break;
+        case WgradFamily::HALO_F16:
+            with_halo(r, [&](auto kr, auto kw, auto sq, auto dil) {
+                with_io(r.io, [&](auto io) {
+                    hipLaunchKernelGGL((wgrad_halo_f16_kernel<kr(), kw(), sq(), dil(), io(), 1>), grid, blk, 0, st, a, r.hdh,
+                                       r.hdw);
+                });
+            });
+            break;
+        case WgradFamily::HALO_B6_PF2:  // one tap row per block (KR = 1)
+            with_halo(r, [&](auto, auto kw, auto sq, auto dil) {
+                hipLaunchKernelGGL((wgrad_halo_bf6_pf2_kernel<kw(), sq(), dil(), halo_pf2_minb(kw(), sq())>), grid, blk, 0,
+                                   st, a, r.hdh, r.hdw);
+            });
+            break;
+        case WgradFamily::HALO_B6:
+            with_halo(r, [&](auto kr, auto kw, auto sq, auto dil) {
+                hipLaunchKernelGGL((wgrad_halo_bf6_kernel<kr(), kw(), sq(), dil()>), grid, blk, 0, st, a, r.hdh, r.hdw);
+            });
+            break;
+        case WgradFamily::HALO:
+            with_halo(r, [&](auto kr, auto kw, auto sq, auto dil) {
+                hipLaunchKernelGGL((wgrad_halo_kernel<kr(), kw(), sq(), dil(), 1>), grid, blk, 0, st, a, r.hdh, r.hdw);
+            });
+            break;
+        case WgradFamily::F16:
+            with_tile(r, [&](auto tm, auto tn, auto wm, auto wn, auto nt) {
+                with_io(r.io, [&](auto io) {
+                    if (r.sqr)  // GDN: Q = x (fp16 in AMP training), P = the norm gradient (fp16 with AMP fp16 gradients)
+                        hipLaunchKernelGGL((wgrad_f16_kernel<tm(), tn(), wm(), wn(), nt(), true, false, io()>), grid, blk, 0, st, a);
+                    else if (nt() == 1 && r.plain)
+                        hipLaunchKernelGGL((wgrad_f16_kernel<tm(), tn(), wm(), wn(), 1, false, true, io()>), grid, blk, 0, st, a);
+                    else
+                        hipLaunchKernelGGL((wgrad_f16_kernel<tm(), tn(), wm(), wn(), nt(), false, false, io()>), grid, blk, 0, st, a);
+                });
+            });
+            break;
+        case WgradFamily::GENERIC:
+            with_tile(r, [&](auto tm, auto tn, auto wm, auto wn, auto nt) { launch_wgrad<tm(), tn(), wm(), wn(), nt()>(a, r, st); });
+            break;
+    }
     int rc = HY_LAUNCH_CHECK("wgrad_kernel");
     if (rc) return rc;
-    const long long total = (long long)d->ntaps * d->M * d->N;
-    const int lx = reduce_lx(total, p.nsplit);
-    jobs[0] = hyres_wgrad_job{(const float*)ws, dst, p.nsplit, d->ntaps, d->M, d->N, d->sm, d->sn, d->st,
-                              d->accumulate, lx, 0};
+    jobs[0] = hyres_wgrad_job{(const float*)ws, dst, r.nsplit, d->ntaps, d->M, d->N, d->sm, d->sn, d->st,
+                              d->accumulate, r.lanes, 0};
     *njobs = 1;
-    if (dbias && !swap) {  // [nsplit][M] partials = a [nsplit][1][M][1] slab, reduced with the weight's layout
-        jobs[1] = hyres_wgrad_job{(const float*)bias_ws, dbias, p.nsplit, 1, d->M, 1, 1, 0, 0, d->accumulate, lx, 0};
+    if (dbias && !r.swap) {  // [nsplit][M] partials = a [nsplit][1][M][1] slab, reduced with the weight's layout
+        jobs[1] = hyres_wgrad_job{(const float*)bias_ws, dbias, r.nsplit, 1, d->M, 1, 1, 0, 0, d->accumulate, r.lanes, 0};
         *njobs = 2;
     }
-    if (dbias && swap) {  // P (= dY) is the tap-folded side here: plain column sums (own workspace after the slab)
+    if (dbias && r.swap) {  // P (= dY) is the tap-folded side here: plain column sums (own workspace after the slab)
         const int P = d0->B * d0->Hq * d0->Wq;
         if (d0->io_f16 & 1)
             return hyres_colsum_f16(p_orig, P, d0->M, d0->ldp, dbias, d0->accumulate, bias_ws,
@@ -2649,6 +2611,53 @@ static int wgrad_issue(const hyres_wgrad_desc* d0, const float* pp, const float*
         return hyres_colsum(p_orig, P, d0->M, d0->ldp, dbias, d0->accumulate, bias_ws,
                             hyres_colsum_workspace_bytes(P, d0->M), s);
     }
+    return 0;
+}
+
+int hyres_wgrad_kernel_name(const hyres_wgrad_desc* d, char* buf, int n) {
+    HY_REQUIRE(d && buf && n > 0, HYRES_E_ARG, "wgrad_kernel_name: bad args");
+    const WgradRoute r = wgrad_route(d, WgradFacts::ideal());
+    auto tf = [](bool b) { return b ? "true" : "false"; };
+    char tile[32];
+    snprintf(tile, sizeof tile, "%d, %d, %d, %d", r.TM, r.TN, r.WM, r.WN);
+    const bool vec = r.vp && r.vq, one16 = r.NT == 1 && r.plain;
+    switch (r.family) {
+        case WgradFamily::GENERIC:
+            snprintf(buf, n, "wgrad_kernel<%s, %d, %s, %s, %s>", tile, r.NT, tf(r.vp), tf(r.vq), tf(vec && r.sqr));
+            break;
+        case WgradFamily::F16:
+            snprintf(buf, n, "wgrad_f16_kernel<%s, %d, %s, %s, %d>", tile, r.NT, tf(r.sqr), tf(one16), r.io);
+            break;
+        case WgradFamily::ONE: snprintf(buf, n, "wgrad1x1_kernel<%s, %d>", tile, r.G); break;
+        case WgradFamily::ONE_B6: snprintf(buf, n, "wgrad1x1_bf6_kernel<%s>", tile); break;
+        case WgradFamily::ONE_B6_PF2: snprintf(buf, n, "wgrad1x1_bf6_pf2_kernel<%s>", tile); break;
+        case WgradFamily::THIN:
+            snprintf(buf, n, "wgrad_thin_kernel<%d, %d, %d, %d, %s>", r.thin.mw, r.thin.nc, r.thin.tg, r.thin.sq,
+                     tf(r.io & 1));
+            break;
+        case WgradFamily::HALO:
+            snprintf(buf, n, "wgrad_halo_kernel<%d, %d, %d, %d, 1>", r.KR, r.KW, r.SQ, r.DIL);
+            break;
+        case WgradFamily::HALO_F16:
+            snprintf(buf, n, "wgrad_halo_f16_kernel<%d, %d, %d, %d, %d, 1>", r.KR, r.KW, r.SQ, r.DIL, r.io);
+            break;
+        case WgradFamily::HALO_B6:
+            snprintf(buf, n, "wgrad_halo_bf6_kernel<%d, %d, %d, %d>", r.KR, r.KW, r.SQ, r.DIL);
+            break;
+        case WgradFamily::HALO_B6_PF2:
+            snprintf(buf, n, "wgrad_halo_bf6_pf2_kernel<%d, %d, %d, %d>", r.KW, r.SQ, r.DIL, halo_pf2_minb(r.KW, r.SQ));
+            break;
+    }
+    return 0;
+}
+
+int hyres_wgrad_plan(const hyres_wgrad_desc* d, int* nsplit, int* blocks, int* threads, int* lanes) {
+    HY_REQUIRE(d, HYRES_E_ARG, "wgrad_plan: NULL argument");
+    const WgradRoute r = wgrad_route(d, WgradFacts::ideal());
+    if (nsplit) *nsplit = r.nsplit;
+    if (blocks) *blocks = (int)(r.grid.x * r.grid.y);
+    if (threads) *threads = (int)r.block.x;
+    if (lanes) *lanes = r.lanes;
     return 0;
 }
 

@@ -589,6 +589,13 @@ def conv_variant(g: L.ConvGeom, e: L.Epilogue, splitk: bool) -> str:
     return buf.value.decode()
 
 
+def wgrad_variant(d: L.WgradDesc) -> str:
+    """The kernel hyres_conv_wgrad launches for d, named by the launcher's own choice function."""
+    buf = ctypes.create_string_buffer(96)
+    L.call("hyres_wgrad_kernel_name", ctypes.byref(d), buf, len(buf))
+    return buf.value.decode()
+
+
 def conv_split(g: L.ConvGeom, e: L.Epilogue) -> int:
     """The split-K factor hyres_conv_forward will use for (g, e) (1 = fused epilogue)."""
     tile, ns = ctypes.c_int(0), ctypes.c_int(1)

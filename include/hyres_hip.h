@@ -252,6 +252,14 @@ int hyres_wgrad_desc_conv2d(hyres_wgrad_desc* d, int B, int H, int W, int Ci, in
 int hyres_wgrad_desc_deconv2d(hyres_wgrad_desc* d, int B, int H, int W, int Ci, int ldx, int Co,
                               int ldy, int K, int pad);
 long long hyres_wgrad_workspace_bytes(const hyres_wgrad_desc* d);
+/* Name of the kernel hyres_conv_wgrad launches for d as rocprof prints it, every template argument spelled out,
+ * e.g. "wgrad_halo_bf6_pf2_kernel<3, 1, 1, 2>" (16B-aligned operands and workspace assumed).  Host-only, no
+ * launch: the launcher's own choice function. */
+int hyres_wgrad_kernel_name(const hyres_wgrad_desc* d, char* buf, int n);
+/* The launcher's plan for d under the same assumption: the split count, the grid (blocks, rounded up to a multiple
+ * of 8; the thin kernel's row blocks x tap groups as they are), the block size and the lanes of the split reduce.
+ * Any output may be NULL.  Pure host function. */
+int hyres_wgrad_plan(const hyres_wgrad_desc* d, int* nsplit, int* blocks, int* threads, int* lanes);
 /* dbias (optional, may be NULL): dbias[m] (+)= sum_q P[q][m] — the Conv2d bias gradient when P = dY
  * (replaces the separate colsum for conv layers; fused into the weight-gradient kernel). */
 int hyres_conv_wgrad(const hyres_wgrad_desc* d, const float* p, const float* q, float* dst,

@@ -690,12 +690,20 @@ def test_wgrad_prefetch2_kernels_bit_identical(K, B, H, W, Ci, Co, key, S):
     d.sm = Ci * K * K
     nb = L.load().hyres_wgrad_workspace_bytes(ctypes.byref(d))
     ws = torch.empty(nb // 4 + 16, device=D)
-    old = ctypes.c_int(0)
+    from hyres_hip import ops as O
+    old, old22 = ctypes.c_int(0), ctypes.c_int(0)
     L.call("hyres_conv_tuning", 7, 1, ctypes.byref(old))
-    res = {}
+    # the 5-tap rows run two chunks ahead only with key 22 = 1 (default 0): without it both values of key 16 name
+    # the one-ahead kernel, and the comparison below would compare a kernel with itself
+    L.call("hyres_conv_tuning", 22, 0, ctypes.byref(old22))
+    res, names = {}, {}
     try:
+        if K == 5:
+            assert "_pf2_" not in O.wgrad_variant(d)
+            L.call("hyres_conv_tuning", 22, 1, None)
         for v in (1, 2):
             L.call("hyres_conv_tuning", key, v, None)
+            names[v] = O.wgrad_variant(d)
             dw = torch.zeros((Co, Ci, K, K), device=D)
             db = torch.zeros((Co,), device=D)
             L.call("hyres_conv_wgrad", ctypes.byref(d), gy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(),
@@ -704,7 +712,10 @@ def test_wgrad_prefetch2_kernels_bit_identical(K, B, H, W, Ci, Co, key, S):
             res[v] = (dw.cpu(), db.cpu())
     finally:
         L.call("hyres_conv_tuning", key, 2, None)
+        L.call("hyres_conv_tuning", 22, old22.value, None)
         L.call("hyres_conv_tuning", 7, old.value, None)
+    stem = "wgrad1x1_bf6" if K == 1 else "wgrad_halo_bf6"
+    assert names[1].startswith(stem + "_kernel<") and names[2].startswith(stem + "_pf2_kernel<"), names
     assert torch.equal(res[1][0], res[2][0]) and torch.equal(res[1][1], res[2][1])
     xr = x.cpu().double().permute(0, 3, 1, 2)
     gr = gy.cpu().double().permute(0, 3, 1, 2)
@@ -763,6 +774,7 @@ def test_wgrad_thin_window_bit_identical(B, H, W, Ci, Co):
     bit, on ragged widths (a partial last 64-pixel chunk), and within 1e-5 of fp64."""
     import ctypes
     from hyres_hip import _lib as L
+    from hyres_hip import ops as O
     D = dev()
     g = torch.Generator().manual_seed(9)
     x = (torch.rand((B, H, W, Ci), generator=g) * 2 - 1).to(D)
@@ -776,6 +788,7 @@ def test_wgrad_thin_window_bit_identical(B, H, W, Ci, Co):
     try:
         for v in (0, 1):
             L.call("hyres_conv_tuning", 23, v, None)
+            assert O.wgrad_variant(d).startswith("wgrad_thin_kernel<"), (v, O.wgrad_variant(d))
             dw = torch.zeros((Co, Ci, 3, 3), device=D)
             db = torch.zeros((Co,), device=D)
             L.call("hyres_conv_wgrad", ctypes.byref(d), gy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(),

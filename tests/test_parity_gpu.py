@@ -68,9 +68,10 @@ CONV_CASES = [
     (1, 3, 64, 6, 256, 3, 1, 2, 2),    # 256-wide row window, dilation 2
     (1, 3, 64, 4, 300, 3, 1, 1, 1),    # window wider than the LDS stage: generic tap-folded path
     (2, 3, 128, 16, 40, 5, 2, 2, 1),   # two tap groups, stride 2
-    # halo-staged weight gradient (wgrad_halo_kernel): base rows a multiple of 32 pixels
-    (2, 64, 64, 32, 32, 3, 1, 1, 1),   # 3x3, all 9 taps per block
-    (2, 64, 64, 20, 64, 3, 1, 2, 2),   # dilated 3x3 (MultiScaleRefine): halo rows 2 apart
+    # halo-staged weight gradient (wgrad_halo_kernel; bf16x6: wgrad_halo_bf6[_pf2]_kernel): base rows a multiple of
+    # 32 pixels
+    (2, 64, 64, 32, 32, 3, 1, 1, 1),   # 3x3, one kernel row of 3 taps per block
+    (2, 64, 64, 20, 64, 3, 1, 2, 2),   # dilated 3x3 (MultiScaleRefine): halo rows 2 apart, all 9 taps per block
     (1, 96, 64, 32, 32, 3, 1, 2, 2),
     (1, 96, 64, 8, 64, 3, 1, 1, 1),    # partial N tile (Ci = 96), two 32-px chunks per row
     (2, 64, 64, 64, 64, 5, 2, 2, 1),   # 5x5 stride 2 (Q stride 2), one kernel row per block
@@ -82,12 +83,45 @@ CONV_CASES = [
     (4, 64, 32, 128, 256, 3, 1, 1, 1),
 ]
 
+# the weight-gradient kernel the cases above name in their comments, as hyres_wgrad_kernel_name reports it (under
+# either fp32 GEMM mode): a case that drifts to another kernel no longer tests what it says
+_HALO3 = r"wgrad_halo_(kernel<1, 3, 1, 1, 1>|bf6_pf2_kernel<3, 1, 1, 2>)"
+_HALO3D = r"wgrad_halo_(bf6_)?kernel<3, 3, 1, 2(, 1)?>"
+WGRAD_KERNELS = {
+    (2, 64, 96, 16, 16, 5, 1, 2, 1): r"wgrad_kernel<1, 1, 2, 2, 5, true, true, false>",
+    (2, 5, 48, 12, 12, 3, 1, 1, 1): r"wgrad_kernel<1, 1, 2, 2, 1, true, false, false>",   # folded: scalar Q loads
+    (2, 48, 5, 12, 12, 3, 1, 1, 1): r"wgrad_kernel<1, 1, 2, 2, 1, true, false, false>",   # swapped: the same
+    (2, 1, 64, 20, 36, 3, 1, 1, 1): r"wgrad_thin_kernel<1, 4, 9, 1, false>",
+    (2, 64, 2, 20, 36, 3, 1, 1, 1): r"wgrad_thin_kernel<1, 4, 9, 1, false>",
+    (1, 3, 64, 6, 256, 3, 1, 2, 2): r"wgrad_thin_kernel<1, 3, 9, 1, false>",
+    (1, 3, 64, 4, 300, 3, 1, 1, 1): r"wgrad_kernel<1, 1, 4, 1, 1, true, false, false>",
+    (2, 3, 128, 16, 40, 5, 2, 2, 1): r"wgrad_thin_kernel<2, 3, 13, 2, false>",
+    (2, 64, 64, 32, 32, 3, 1, 1, 1): _HALO3,
+    (2, 64, 64, 20, 64, 3, 1, 2, 2): _HALO3D,
+    (1, 96, 64, 32, 32, 3, 1, 2, 2): _HALO3D,
+    (1, 96, 64, 8, 64, 3, 1, 1, 1): _HALO3,
+    (2, 64, 64, 64, 64, 5, 2, 2, 1): r"wgrad_halo_(bf6_)?kernel<1, 5, 2, 1(, 1)?>",
+    (2, 64, 128, 32, 64, 5, 1, 2, 1): r"wgrad_halo_(bf6_)?kernel<1, 5, 1, 1(, 1)?>",
+}
+
+
+def _assert_wgrad_kernel(pattern, fn, *args, f16=False):
+    import re
+    from hyres_hip import _lib as L
+    from hyres_hip import ops as O
+    d = L.WgradDesc()
+    L.call(fn, ctypes.byref(d), *args)
+    d.f16_operands = int(f16)
+    assert re.fullmatch(pattern, O.wgrad_variant(d)), (O.wgrad_variant(d), pattern)
+
 
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv2d_fwd_bwd(case, fp32_gemm):
     from hyres_hip import _lib as L
     from hyres_hip import ops as O
     B, Ci, Co, H, W, K, s, p, d = case
+    if case in WGRAD_KERNELS:
+        _assert_wgrad_kernel(WGRAD_KERNELS[case], "hyres_wgrad_desc_conv2d", B, H, W, Ci, Ci, Co, Co, K, K, s, p, d)
     x = _rand((B, Ci, H, W), 1)
     w = _rand((Co, Ci, K, K), 2, 1.0 / (Ci * K * K) ** 0.5)
     b = _rand((Co,), 3, 0.1)
@@ -166,6 +200,9 @@ def test_conv1x1_epilogue_chain(case, fp32_gemm):
 def test_deconv2d_fwd_bwd(case, fp32_gemm):
     from hyres_hip import ops as O
     B, Ci, Co, H, W = case
+    if case == (2, 64, 64, 32, 32):
+        _assert_wgrad_kernel(r"wgrad_halo_(bf6_)?kernel<1, 5, 2, 1(, 1)?>", "hyres_wgrad_desc_deconv2d", B, H, W, Ci, Ci,
+                             Co, Co, 5, 2)
     x = _rand((B, Ci, H, W), 5)
     w = _rand((Ci, Co, 5, 5), 6, 1.0 / (Ci * 25 / 4) ** 0.5)
     b = _rand((Co,), 7, 0.1)
@@ -1854,6 +1891,11 @@ def test_conv2d_amp_fwd_bwd(case):
     dx = conv^T(gy_h, w_h), dw = sum gy_h x_h, db = sum gy (only the summation order differs: 1e-5)."""
     from hyres_hip import ops as O
     B, Ci, Co, H, W, K, s, p, d = case
+    halo16 = {(2, 64, 64, 32, 32, 3, 1, 1, 1): "1, 3, 1, 1", (2, 64, 96, 32, 64, 3, 1, 2, 2): "3, 3, 1, 2",
+              (2, 64, 96, 64, 64, 5, 2, 2, 1): "1, 5, 2, 1"}
+    if case in halo16:
+        _assert_wgrad_kernel(rf"wgrad_halo_f16_kernel<{halo16[case]}, \d, 1>", "hyres_wgrad_desc_conv2d", B, H, W, Ci,
+                             Ci, Co, Co, K, K, s, p, d, f16=True)
     x = _rand((B, Ci, H, W), 41)
     w = _rand((Co, Ci, K, K), 42, 1.0 / (Ci * K * K) ** 0.5)
     b = _rand((Co,), 43, 0.1)
@@ -1886,6 +1928,9 @@ def test_deconv2d_amp_fwd_bwd(hw):
     (hw = 32: rows of 32 pixels, the f16 halo-staged weight gradient)."""
     from hyres_hip import ops as O
     B, Ci, Co, H, W = 2, 128, 128, hw, hw
+    if hw == 32:
+        _assert_wgrad_kernel(r"wgrad_halo_f16_kernel<1, 5, 2, 1, \d, 1>", "hyres_wgrad_desc_deconv2d", B, H, W, Ci, Ci,
+                             Co, Co, 5, 2, f16=True)
     x = _rand((B, Ci, H, W), 45)
     w = _rand((Ci, Co, 5, 5), 46, 1.0 / (Ci * 25 / 4) ** 0.5)
     b = _rand((Co,), 47, 0.1)

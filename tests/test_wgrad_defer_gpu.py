@@ -16,8 +16,8 @@ from helpers import build_model, load_npz
 pytestmark = pytest.mark.gpu
 
 # (B, H, W, Ci, Co, K, stride, pad, dil, bias, f16): the halo 3x3 (fp32 / AMP), dilated 3x3, 1x1 with a bias
-# (wgrad1x1, two groups), a 5x5 stride-2, the 3-channel image layer (swapped, colsum bias), a thin layer
-# (Co = 3) and a small 32^2 grid with many splits
+# (the plain-1x1 kernels; 16384 pixels: one 4-wave group), a 5x5 stride-2, the 3-channel image layer at stride 2
+# (thin), a Co = 3 layer (swapped onto the thin kernel, colsum bias) and a small grid with many splits
 CASES = [
     (4, 64, 64, 64, 64, 3, 1, 1, 1, True, False),
     (4, 64, 64, 64, 64, 3, 1, 1, 1, True, True),
@@ -27,6 +27,17 @@ CASES = [
     (2, 64, 64, 3, 64, 5, 2, 2, 1, True, False),
     (2, 64, 64, 64, 3, 3, 1, 1, 1, True, False),
     (16, 16, 16, 96, 96, 3, 1, 1, 1, True, False),
+]
+# ... and the kernel each case names, as hyres_wgrad_kernel_name reports it (under either fp32 GEMM mode)
+KERNELS = [
+    r"wgrad_halo_(kernel<1, 3, 1, 1, 1>|bf6_pf2_kernel<3, 1, 1, 2>)",
+    r"wgrad_halo_f16_kernel<1, 3, 1, 1, 0, 1>",
+    r"wgrad_halo_(bf6_)?kernel<3, 3, 1, 2(, 1)?>",
+    r"wgrad1x1_(kernel<1, 1, 2, 2, 1>|bf6_pf2_kernel<1, 1, 2, 2>)",
+    r"wgrad_halo_(bf6_)?kernel<1, 5, 2, 1(, 1)?>",
+    r"wgrad_thin_kernel<1, 3, 25, 2, false>",
+    r"wgrad_thin_kernel<1, 3, 9, 1, false>",
+    r"wgrad_kernel<1, 1, 2, 2, 9, true, true, false>",
 ]
 
 
@@ -69,8 +80,13 @@ def _run(L, lib, case, deferred, seed=0):
 
 @pytest.mark.parametrize("case", CASES)
 def test_deferred_reduce_bit_identical(case):
+    import re
+
     import hyres_hip._lib as L
+    from hyres_hip import ops as O
     lib = L.load()
+    name = O.wgrad_variant(_desc(L, *case[:9], case[10]))
+    assert re.fullmatch(KERNELS[CASES.index(case)], name), name
     dw0, db0, (x, gy) = _run(L, lib, case, deferred=False)
     dw1, db1, _ = _run(L, lib, case, deferred=True)
     assert torch.equal(dw0, dw1)
