@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "hyres_hip.h"
 
@@ -23,7 +24,23 @@ inline int launch_status(const char* what) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+// a 4-element vector of the operand: 8 B as fp16, 16 B as fp32
+inline bool aligned_v4(const void* p, bool half) { return half ? aligned8(p) : aligned16(p); }
+
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// Operand dtypes of the element-wise and MultiScaleRefine entry points (HYRES_DT_*, hyres_hip.h). The masks that have
+// kernels: fp32, fp16 saved activations, fp16 activations with fp16 gradients. dispatch_hg calls f(H, G) with the two
+// flags as std::bool_constant values, which serve as template arguments inside f.
+inline bool dt_valid(int dt) { return dt == 0 || dt == HYRES_DT_ACT16 || dt == (HYRES_DT_ACT16 | HYRES_DT_GRAD16); }
+inline bool f16_valid(int f16) { return f16 == 0 || f16 == 1; }
+template <class F>
+inline int dispatch_hg(int dt, F&& f) {
+    if (dt & HYRES_DT_GRAD16) return f(std::true_type{}, std::true_type{});
+    if (dt & HYRES_DT_ACT16) return f(std::true_type{}, std::false_type{});
+    return f(std::false_type{}, std::false_type{});
+}
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -69,5 +86,10 @@ __device__ __forceinline__ void stv4(float* p, long long i, float4 v) {
     do {                                                             \
         if (!(cond)) return ::hyres::set_error((code), __VA_ARGS__); \
     } while (0)
+
+#define HY_REQUIRE_DT(dt, op)                                                                                         \
+    HY_REQUIRE(::hyres::dt_valid(dt), HYRES_E_ARG,                                                                    \
+               op ": dt %d: 0, ACT16 or ACT16 | GRAD16 (no fp16 gradients of fp32 activations)", (dt))
+#define HY_REQUIRE_F16(f16, op) HY_REQUIRE(::hyres::f16_valid(f16), HYRES_E_ARG, op ": f16 %d: 0 or 1", (f16))
 
 #define HY_LAUNCH_CHECK(name) ::hyres::launch_status(name)

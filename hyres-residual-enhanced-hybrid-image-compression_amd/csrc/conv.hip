@@ -2993,7 +2993,6 @@ struct ConvFacts {
     static ConvFacts ideal() { return {true, true, true, true, true, std::numeric_limits<long long>::max(), true}; }
 };
 
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 static bool fits32(long long bytes) { return bytes < 0x7FFFFFF0LL; }
 
 static int pack_cfg(int nt, int k, int f) { return nt | (k << 4) | (f << 12); }

@@ -577,14 +577,12 @@ static int relu_bwd_2d_impl(const float* y, int ldy, const float* g, int ldg, fl
     return HY_LAUNCH_CHECK("relu_bwd_2d");
 }
 }  // extern "C++"
-int hyres_relu_bwd_2d(const float* y, int ldy, const float* g, int ldg, float* gx, int ldgx, long long P, int C,
+int hyres_relu_bwd_2d(const void* y, int ldy, const void* g, int ldg, void* gx, int ldgx, long long P, int C, int dt,
                       hyres_stream_t s) {
-    return relu_bwd_2d_impl<false, false>(y, ldy, g, ldg, gx, ldgx, P, C, s);
-}
-int hyres_relu_bwd_2d_f16(const void* y, int ldy, const void* g, int ldg, void* gx, int ldgx, long long P, int C,
-                          int g16, hyres_stream_t s) {
-    if (g16) return relu_bwd_2d_impl<true, true>((const float*)y, ldy, (const float*)g, ldg, (float*)gx, ldgx, P, C, s);
-    return relu_bwd_2d_impl<true, false>((const float*)y, ldy, (const float*)g, ldg, (float*)gx, ldgx, P, C, s);
+    HY_REQUIRE_DT(dt, "relu_bwd_2d");
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        return relu_bwd_2d_impl<H, G>((const float*)y, ldy, (const float*)g, ldg, (float*)gx, ldgx, P, C, s);
+    });
 }
 long long hyres_reduce_workspace_bytes(long long n) { return (long long)grid_for(n, 4) * 8 + 256; }  // fp64 partials
 
@@ -607,105 +605,76 @@ static int prelu_bwd_impl(const float* x, int ldx, const float* g, int ldg, floa
     return HY_LAUNCH_CHECK("prelu_bwd_final");
 }
 }  // extern "C++"
-int hyres_prelu_bwd(const float* x, int ldx, const float* g, int ldg, float* gx, int ldgx, long long P, int C,
-                    const float* slope, float* dslope, void* ws, long long ws_bytes, hyres_stream_t s) {
-    return prelu_bwd_impl<false, false>(x, ldx, g, ldg, gx, ldgx, P, C, slope, dslope, ws, ws_bytes, s);
+int hyres_prelu_bwd(const void* x, int ldx, const void* g, int ldg, void* gx, int ldgx, long long P, int C,
+                    const float* slope, float* dslope, void* ws, long long ws_bytes, int dt, hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "prelu_bwd");
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        return prelu_bwd_impl<H, G>((const float*)x, ldx, (const float*)g, ldg, (float*)gx, ldgx, P, C, slope, dslope,
+                                    ws, ws_bytes, s);
+    });
 }
-int hyres_prelu_bwd_f16(const void* x, int ldx, const void* g, int ldg, void* gx, int ldgx, long long P, int C,
-                        const float* slope, float* dslope, void* ws, long long ws_bytes, int g16, hyres_stream_t s) {
-    if (g16)
-        return prelu_bwd_impl<true, true>((const float*)x, ldx, (const float*)g, ldg, (float*)gx, ldgx, P, C, slope,
-                                          dslope, ws, ws_bytes, s);
-    return prelu_bwd_impl<true, false>((const float*)x, ldx, (const float*)g, ldg, (float*)gx, ldgx, P, C, slope, dslope,
-                                       ws, ws_bytes, s);
-}
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-int hyres_attn_gate_fwd(const float* a, const float* b, const float* x, float* out, long long n, hyres_stream_t s) {
+int hyres_attn_gate_fwd(const void* a, const void* b, const void* x, void* out, long long n, int f16, hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "attn_gate_fwd");
     HY_REQUIRE(a && b && x && out, HYRES_E_ARG, "attn_gate_fwd: NULL");
-    if (n % 4 == 0 && al16(a) && al16(b) && al16(x) && al16(out)) {
-        hipLaunchKernelGGL(attn_gate_fwd4_kernel, dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s), a, b, x, out, n / 4);
+    const float *af = (const float*)a, *bf = (const float*)b, *xf = (const float*)x;
+    float* of = (float*)out;
+    if (f16) {  // the 4-vector kernel only
+        HY_REQUIRE(n % 4 == 0, HYRES_E_ARG, "attn_gate_fwd: fp16 needs n %% 4 == 0");
+        hipLaunchKernelGGL(attn_gate_fwd4h_kernel, dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s), af, bf, xf, of, n / 4);
+        return HY_LAUNCH_CHECK("attn_gate_fwd4h");
+    }
+    if (n % 4 == 0 && aligned16(a) && aligned16(b) && aligned16(x) && aligned16(out)) {
+        hipLaunchKernelGGL(attn_gate_fwd4_kernel, dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s), af, bf, xf, of, n / 4);
         return HY_LAUNCH_CHECK("attn_gate_fwd4");
     }
-    hipLaunchKernelGGL(attn_gate_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(s), a, b, x, out, n);
+    hipLaunchKernelGGL(attn_gate_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(s), af, bf, xf, of, n);
     return HY_LAUNCH_CHECK("attn_gate_fwd");
 }
-int hyres_attn_gate_fwd_f16(const void* a, const void* b, const void* x, void* out, long long n, hyres_stream_t s) {
-    HY_REQUIRE(a && b && x && out && n % 4 == 0, HYRES_E_ARG, "attn_gate_fwd_f16: NULL or n %% 4 != 0");
-    hipLaunchKernelGGL(attn_gate_fwd4h_kernel, dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s), (const float*)a,
-                       (const float*)b, (const float*)x, (float*)out, n / 4);
-    return HY_LAUNCH_CHECK("attn_gate_fwd_f16");
-}
-int hyres_attn_gate_bwd_relu(const float* a, const float* b, const float* g, float* ga, float* gb, long long n,
-                             hyres_stream_t s) {
-    HY_REQUIRE(a && b && g && ga && gb && n % 4 == 0 && al16(a) && al16(b) && al16(g) && al16(ga) && al16(gb), HYRES_E_ARG,
-               "attn_gate_bwd_relu: NULL, n %% 4 != 0 or an operand not 16B-aligned");
-    hipLaunchKernelGGL((attn_gate_bwd4_kernel<false, false, true>), dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s), a,
-                       b, g, ga, gb, n / 4);
-    return HY_LAUNCH_CHECK("attn_gate_bwd4");
-}
-int hyres_attn_gate_bwd(const float* a, const float* b, const float* g, float* ga, float* gb, long long n,
-                        hyres_stream_t s) {
-    HY_REQUIRE(a && b && g && ga && gb, HYRES_E_ARG, "attn_gate_bwd: NULL");
-    if (n % 4 == 0 && al16(a) && al16(b) && al16(g) && al16(ga) && al16(gb)) {
-        hipLaunchKernelGGL((attn_gate_bwd4_kernel<false, false, false>), dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s),
-                           a, b, g, ga, gb, n / 4);
-        return HY_LAUNCH_CHECK("attn_gate_bwd4");
-    }
-    hipLaunchKernelGGL((attn_gate_bwd_kernel<false, false>), dim3(grid_for(n)), dim3(256), 0, as_stream(s), a, b, g,
-                       ga, gb, n);
-    return HY_LAUNCH_CHECK("attn_gate_bwd");
-}
-static bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-// the vector path of the fp16-activation gate backward: n % 4 == 0, fp16 operands 8B-aligned, fp32 ones 16B-aligned
-static bool gate_f16_vec(const void* a, const void* b, const void* g, const void* ga, const void* gb, long long n,
-                         int g16) {
-    auto gal = [&](const void* p) { return g16 ? al8(p) : al16(p); };
-    return n % 4 == 0 && al8(a) && al8(b) && gal(g) && gal(ga) && gal(gb);
+// the vector path of the gate backward: n % 4 == 0, fp16 operands 8B-aligned, fp32 ones 16B-aligned
+static bool gate_bwd_vec(const void* a, const void* b, const void* g, const void* ga, const void* gb, long long n, int dt) {
+    const bool h = dt & HYRES_DT_ACT16, g16 = dt & HYRES_DT_GRAD16;
+    return n % 4 == 0 && aligned_v4(a, h) && aligned_v4(b, h) && aligned_v4(g, g16) && aligned_v4(ga, g16) &&
+           aligned_v4(gb, g16);
 }
 extern "C++" {
 template <bool MASK>
-static void launch_gate_bwd4h(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int g16,
-                              hipStream_t st) {
-    if (g16)
-        hipLaunchKernelGGL((attn_gate_bwd4_kernel<true, true, MASK>), dim3(grid_for(n / 4)), dim3(256), 0, st,
+static int launch_gate_bwd4(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int dt,
+                            hyres_stream_t s) {
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        hipLaunchKernelGGL((attn_gate_bwd4_kernel<H, G, MASK>), dim3(grid_for(n / 4)), dim3(256), 0, as_stream(s),
                            (const float*)a, (const float*)b, (const float*)g, (float*)ga, (float*)gb, n / 4);
-    else
-        hipLaunchKernelGGL((attn_gate_bwd4_kernel<true, false, MASK>), dim3(grid_for(n / 4)), dim3(256), 0, st,
-                           (const float*)a, (const float*)b, (const float*)g, (float*)ga, (float*)gb, n / 4);
+        return HY_LAUNCH_CHECK("attn_gate_bwd4");
+    });
 }
 }  // extern "C++"
-int hyres_attn_gate_bwd_relu_f16(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int g16,
-                                 hyres_stream_t s) {
-    HY_REQUIRE(a && b && g && ga && gb && gate_f16_vec(a, b, g, ga, gb, n, g16), HYRES_E_ARG,
-               "attn_gate_bwd_relu_f16: NULL, n %% 4 != 0 or a misaligned operand");
-    launch_gate_bwd4h<true>(a, b, g, ga, gb, n, g16, as_stream(s));
-    return HY_LAUNCH_CHECK("attn_gate_bwd4h");
+int hyres_attn_gate_bwd_relu(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int dt,
+                             hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "attn_gate_bwd_relu");
+    HY_REQUIRE(a && b && g && ga && gb && gate_bwd_vec(a, b, g, ga, gb, n, dt), HYRES_E_ARG,
+               "attn_gate_bwd_relu: NULL, n %% 4 != 0 or a misaligned operand");
+    return launch_gate_bwd4<true>(a, b, g, ga, gb, n, dt, s);
 }
-int hyres_attn_gate_bwd_f16(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int g16,
-                            hyres_stream_t s) {
-    HY_REQUIRE(a && b && g && ga && gb, HYRES_E_ARG, "attn_gate_bwd_f16: NULL");
-    if (gate_f16_vec(a, b, g, ga, gb, n, g16)) {
-        launch_gate_bwd4h<false>(a, b, g, ga, gb, n, g16, as_stream(s));
-        return HY_LAUNCH_CHECK("attn_gate_bwd4h");
-    }
-    if (g16)
-        hipLaunchKernelGGL((attn_gate_bwd_kernel<true, true>), dim3(grid_for(n)), dim3(256), 0, as_stream(s),
-                           (const float*)a, (const float*)b, (const float*)g, (float*)ga, (float*)gb, n);
-    else
-        hipLaunchKernelGGL((attn_gate_bwd_kernel<true, false>), dim3(grid_for(n)), dim3(256), 0, as_stream(s),
-                           (const float*)a, (const float*)b, (const float*)g, (float*)ga, (float*)gb, n);
-    return HY_LAUNCH_CHECK("attn_gate_bwd_f16");
+int hyres_attn_gate_bwd(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int dt,
+                        hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "attn_gate_bwd");
+    HY_REQUIRE(a && b && g && ga && gb, HYRES_E_ARG, "attn_gate_bwd: NULL");
+    if (gate_bwd_vec(a, b, g, ga, gb, n, dt)) return launch_gate_bwd4<false>(a, b, g, ga, gb, n, dt, s);
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        hipLaunchKernelGGL((attn_gate_bwd_kernel<H, G>), dim3(grid_for(n)), dim3(256), 0, as_stream(s), (const float*)a,
+                           (const float*)b, (const float*)g, (float*)ga, (float*)gb, n);
+        return HY_LAUNCH_CHECK("attn_gate_bwd");
+    });
 }
-int hyres_accumulate(const float* x, float* y, long long n, hyres_stream_t s) {
+int hyres_accumulate(const void* x, void* y, long long n, int f16, hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "accumulate");
     HY_REQUIRE(x && y, HYRES_E_ARG, "accumulate: NULL");
-    hipLaunchKernelGGL(accumulate_kernel<false>, dim3(grid_for(n)), dim3(256), 0, as_stream(s), x, y, n);
+    if (f16)
+        hipLaunchKernelGGL(accumulate_kernel<true>, dim3(grid_for(n)), dim3(256), 0, as_stream(s), (const float*)x,
+                           (float*)y, n);
+    else
+        hipLaunchKernelGGL(accumulate_kernel<false>, dim3(grid_for(n)), dim3(256), 0, as_stream(s), (const float*)x,
+                           (float*)y, n);
     return HY_LAUNCH_CHECK("accumulate");
-}
-int hyres_accumulate_f16(const void* x, void* y, long long n, hyres_stream_t s) {
-    HY_REQUIRE(x && y, HYRES_E_ARG, "accumulate_f16: NULL");
-    hipLaunchKernelGGL(accumulate_kernel<true>, dim3(grid_for(n)), dim3(256), 0, as_stream(s), (const float*)x,
-                       (float*)y, n);
-    return HY_LAUNCH_CHECK("accumulate_f16");
 }
 extern "C++" {
 template <bool XH, bool YH>
@@ -720,20 +689,16 @@ static int add2d_impl(const float* x, int ldx, float* y, int ldy, long long P, i
     return HY_LAUNCH_CHECK("add2d");
 }
 }  // extern "C++"
-int hyres_add2d(const float* x, int ldx, float* y, int ldy, long long P, int C, int accumulate,
+int hyres_add2d(const void* x, int ldx, void* y, int ldy, long long P, int C, int accumulate, int io,
                 hyres_stream_t s) {
+    HY_REQUIRE(io >= 0 && io <= (HYRES_IO_X16 | HYRES_IO_Y16), HYRES_E_ARG, "add2d: io %d", io);
     HY_REQUIRE(x && y, HYRES_E_ARG, "add2d: NULL");
-    return add2d_impl<false, false>(x, ldx, y, ldy, P, C, accumulate, s);
-}
-int hyres_add2d_f16(const void* x, int ldx, void* y, int ldy, long long P, int C, int accumulate, int io,
-                    hyres_stream_t s) {
-    HY_REQUIRE(x && y && io >= 0 && io <= 3, HYRES_E_ARG, "add2d_f16: NULL or io %d", io);
     const float* xf = (const float*)x;
     float* yf = (float*)y;
     switch (io) {
-        case 1: return add2d_impl<true, false>(xf, ldx, yf, ldy, P, C, accumulate, s);
-        case 2: return add2d_impl<false, true>(xf, ldx, yf, ldy, P, C, accumulate, s);
-        case 3: return add2d_impl<true, true>(xf, ldx, yf, ldy, P, C, accumulate, s);
+        case HYRES_IO_X16: return add2d_impl<true, false>(xf, ldx, yf, ldy, P, C, accumulate, s);
+        case HYRES_IO_Y16: return add2d_impl<false, true>(xf, ldx, yf, ldy, P, C, accumulate, s);
+        case HYRES_IO_X16 | HYRES_IO_Y16: return add2d_impl<true, true>(xf, ldx, yf, ldy, P, C, accumulate, s);
         default: return add2d_impl<false, false>(xf, ldx, yf, ldy, P, C, accumulate, s);
     }
 }
@@ -761,25 +726,16 @@ int hyres_gdn_reparam_bwd(const float* beta, const float* gamma, const float* db
                        gamma, dbp, dgp, db, dg, C, accumulate);
     return HY_LAUNCH_CHECK("gdn_reparam_bwd");
 }
-int hyres_gdn_dnorm(const float* g, const float* y, const float* n, float* dn, long long P, int C, int inverse,
+int hyres_gdn_dnorm(const void* g, const void* y, const void* n, void* dn, long long P, int C, int inverse, int dt,
                     hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "gdn_dnorm");
     HY_REQUIRE(g && y && n && dn, HYRES_E_ARG, "gdn_dnorm: NULL");
     long long cnt = P * C;
-    hipLaunchKernelGGL((gdn_dnorm_kernel<false, false>), dim3(grid_for(cnt)), dim3(256), 0, as_stream(s), g, y, n, dn,
-                       cnt, inverse ? 0.5f : -0.5f);
-    return HY_LAUNCH_CHECK("gdn_dnorm");
-}
-int hyres_gdn_dnorm_f16(const void* g, const void* y, const void* n, void* dn, long long P, int C, int inverse, int g16,
-                        hyres_stream_t s) {
-    HY_REQUIRE(g && y && n && dn, HYRES_E_ARG, "gdn_dnorm_f16: NULL");
-    long long cnt = P * C;
-    if (g16)
-        hipLaunchKernelGGL((gdn_dnorm_kernel<true, true>), dim3(grid_for(cnt)), dim3(256), 0, as_stream(s),
-                           (const float*)g, (const float*)y, (const float*)n, (float*)dn, cnt, inverse ? 0.5f : -0.5f);
-    else
-        hipLaunchKernelGGL((gdn_dnorm_kernel<true, false>), dim3(grid_for(cnt)), dim3(256), 0, as_stream(s),
-                           (const float*)g, (const float*)y, (const float*)n, (float*)dn, cnt, inverse ? 0.5f : -0.5f);
-    return HY_LAUNCH_CHECK("gdn_dnorm_f16");
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        hipLaunchKernelGGL((gdn_dnorm_kernel<H, G>), dim3(grid_for(cnt)), dim3(256), 0, as_stream(s), (const float*)g,
+                           (const float*)y, (const float*)n, (float*)dn, cnt, inverse ? 0.5f : -0.5f);
+        return HY_LAUNCH_CHECK("gdn_dnorm");
+    });
 }
 int hyres_uniform_noise(float* out, long long n, unsigned long long seed, unsigned long long offset,
                         hyres_stream_t s) {

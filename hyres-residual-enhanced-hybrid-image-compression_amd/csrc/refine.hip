@@ -895,31 +895,27 @@ using namespace hyres;
 
 extern "C" {
 
-int hyres_bilinear_fwd(const float* x, int ldx, float* y, int ldy, int B, int Hi, int Wi, int Ho, int Wo, int C,
-                       float scale_h, float scale_w, int accumulate, hyres_stream_t s) {
+int hyres_bilinear_fwd(const void* xv, int ldx, void* yv, int ldy, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                       float scale_h, float scale_w, int accumulate, int f16, hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "bilinear_fwd");
+    HY_REQUIRE(!(f16 && accumulate), HYRES_E_ARG, "bilinear_fwd: no accumulate with fp16");
+    const float* x = (const float*)xv;
+    float* y = (float*)yv;
     HY_REQUIRE(x && y && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, HYRES_E_ARG, "bilinear_fwd: bad args");
-    const bool vec = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y);
+    const bool vec = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned_v4(x, f16) && aligned_v4(y, f16);
+    HY_REQUIRE(vec || !f16, HYRES_E_ALIGN, "bilinear_fwd: fp16 needs C, ld %% 4 == 0 and 8B-aligned x/y");
     HY_REQUIRE((long long)B * Ho <= 65535 && (long long)Wo * C < (1LL << 30), HYRES_E_SHAPE, "bilinear_fwd: too large");
     const dim3 grid(ceil_div((long long)Wo * (vec ? C / 4 : C), 256), B * Ho);
-    if (vec)
+    if (f16)
+        hipLaunchKernelGGL((bilinear_fwd_kernel<4, true>), grid, dim3(256), 0, as_stream(s), x, ldx, y, ldy, B, Hi, Wi, Ho,
+                           Wo, C, scale_h, scale_w, 0);
+    else if (vec)
         hipLaunchKernelGGL(bilinear_fwd_kernel<4>, grid, dim3(256), 0, as_stream(s), x, ldx, y, ldy, B, Hi, Wi, Ho, Wo,
                            C, scale_h, scale_w, accumulate);
     else
         hipLaunchKernelGGL(bilinear_fwd_kernel<1>, grid, dim3(256), 0, as_stream(s), x, ldx, y, ldy, B, Hi, Wi, Ho, Wo,
                            C, scale_h, scale_w, accumulate);
     return HY_LAUNCH_CHECK("bilinear_fwd");
-}
-int hyres_bilinear_fwd_f16(const void* x, int ldx, void* y, int ldy, int B, int Hi, int Wi, int Ho, int Wo, int C,
-                           float scale_h, float scale_w, hyres_stream_t s) {
-    HY_REQUIRE(x && y && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, HYRES_E_ARG, "bilinear_fwd_f16: bad args");
-    HY_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(y) & 7) == 0,
-               HYRES_E_ALIGN, "bilinear_fwd_f16: C, ld %% 4 == 0 and 8B-aligned x/y required");
-    HY_REQUIRE((long long)B * Ho <= 65535 && (long long)Wo * C < (1LL << 30), HYRES_E_SHAPE, "bilinear_fwd_f16: too large");
-    const dim3 grid(ceil_div((long long)Wo * (C / 4), 256), B * Ho);
-    hipLaunchKernelGGL((bilinear_fwd_kernel<4, true>), grid, dim3(256), 0, as_stream(s), (const float*)x, ldx, (float*)y,
-                       ldy, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w, 0);
-    return HY_LAUNCH_CHECK("bilinear_fwd_f16");
 }
 extern "C++" {
 template <bool G>
@@ -957,13 +953,13 @@ long long hyres_bilinear_bwd_prelu_workspace_bytes(int B, int Hi, int Wi, int C)
 }
 int hyres_bilinear_bwd_prelu(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
                              float scale_h, float scale_w, const void* pre, int ldpre, const float* slope, float* dslope,
-                             void* ws, long long ws_bytes, int io, hyres_stream_t s) {
-    HY_REQUIRE(gy && gx && pre && slope && dslope && ws && io >= 0 && io <= 3, HYRES_E_ARG, "bilinear_bwd_prelu: NULL / io");
-    const bool G = io & 1, H = io & 2;
-    const unsigned ag = G ? 7u : 15u, ap = H ? 7u : 15u;
-    HY_REQUIRE(C % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && ldpre % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(gy) & ag) == 0 && (reinterpret_cast<uintptr_t>(gx) & ag) == 0 &&
-                   (reinterpret_cast<uintptr_t>(pre) & ap) == 0,
+                             void* ws, long long ws_bytes, int dt, hyres_stream_t s) {
+    // every mask of the two bits has a kernel here (fp16 gradients over an fp32 pre-activation included)
+    HY_REQUIRE(dt >= 0 && dt <= (HYRES_DT_ACT16 | HYRES_DT_GRAD16), HYRES_E_ARG, "bilinear_bwd_prelu: dt %d", dt);
+    HY_REQUIRE(gy && gx && pre && slope && dslope && ws, HYRES_E_ARG, "bilinear_bwd_prelu: NULL");
+    const bool G = dt & HYRES_DT_GRAD16, H = dt & HYRES_DT_ACT16;
+    HY_REQUIRE(C % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && ldpre % 4 == 0 && aligned_v4(gy, G) && aligned_v4(gx, G) &&
+                   aligned_v4(pre, H),
                HYRES_E_ALIGN, "bilinear_bwd_prelu: C %% 4 == 0, aligned rows");
     HY_REQUIRE((long long)B * Hi <= 65535 && (long long)Wi * C < (1LL << 30), HYRES_E_SHAPE, "bilinear_bwd_prelu: too large");
     HY_REQUIRE(ws_bytes >= hyres_bilinear_bwd_prelu_workspace_bytes(B, Hi, Wi, C), HYRES_E_WORKSPACE,
@@ -992,28 +988,37 @@ int hyres_bilinear_bwd_prelu(const void* gy, int ldgy, void* gx, int ldgx, int B
     hipLaunchKernelGGL(slope_sum8_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)(grid.x * grid.y), dslope);
     return HY_LAUNCH_CHECK("bilinear_bwd_prelu_final");
 }
-int hyres_bilinear_bwd(const float* gy, int ldgy, float* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
-                       float scale_h, float scale_w, int accumulate, hyres_stream_t s) {
-    return bilinear_bwd_impl<false>(gy, ldgy, gx, ldgx, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w, accumulate, s);
-}
-int hyres_bilinear_bwd_f16(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
-                           float scale_h, float scale_w, int accumulate, hyres_stream_t s) {
-    return bilinear_bwd_impl<true>((const float*)gy, ldgy, (float*)gx, ldgx, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w,
-                                   accumulate, s);
+int hyres_bilinear_bwd(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                       float scale_h, float scale_w, int accumulate, int f16, hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "bilinear_bwd");
+    if (f16)
+        return bilinear_bwd_impl<true>((const float*)gy, ldgy, (float*)gx, ldgx, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w,
+                                       accumulate, s);
+    return bilinear_bwd_impl<false>((const float*)gy, ldgy, (float*)gx, ldgx, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w,
+                                    accumulate, s);
 }
 
 static int se_chunks(int HW) { return std::max(1, std::min(64, (HW + 1023) / 1024)); }
 
 long long hyres_se_workspace_bytes(int B, int HW, int C) { return (long long)B * se_chunks(HW) * C * 4; }
 
-int hyres_se_fwd(const float* x, const float* w1, const float* w2, float* y, float* pooled, float* hidden,
-                 float* sgate, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, hyres_stream_t s) {
+int hyres_se_fwd(const void* xv, const float* w1, const float* w2, void* yv, float* pooled, float* hidden,
+                 float* sgate, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, int f16, hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "se_fwd");
+    const float* x = (const float*)xv;
+    float* y = (float*)yv;
     HY_REQUIRE(x && w1 && w2 && y && pooled && hidden && sgate, HYRES_E_ARG, "se_fwd: NULL");
+    // fp16 x / y: the 4-vector kernels only
+    HY_REQUIRE(!f16 || (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && aligned8(x) && aligned8(y)), HYRES_E_ALIGN,
+               "se_fwd: fp16 needs C %% 4 == 0, 256 %% (C/4) == 0, 8B-aligned x/y");
     const int nch = se_chunks(HW);
     HY_REQUIRE(ws && ws_bytes >= (long long)B * nch * C * 4, HYRES_E_WORKSPACE, "se_fwd: workspace");
     const int per = (HW + nch - 1) / nch;
     hipStream_t st = as_stream(s);
-    if (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && aligned16(x))
+    if (f16)
+        hipLaunchKernelGGL((se_pool4_kernel<false, true>), dim3(B, nch), dim3(256), 0, st, x, (const float*)nullptr, HW, C,
+                           per, (float*)ws);
+    else if (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && aligned16(x))
         hipLaunchKernelGGL(se_pool4_kernel<false>, dim3(B, nch), dim3(256), 0, st, x, (const float*)nullptr, HW, C,
                            per, (float*)ws);
     else
@@ -1025,37 +1030,16 @@ int hyres_se_fwd(const float* x, const float* w1, const float* w2, float* y, flo
     rc = HY_LAUNCH_CHECK("se_fc");
     if (rc) return rc;
     long long n = (long long)B * HW * C;
-    if (C % 4 == 0 && aligned16(x) && aligned16(y) && n / 4 < (1LL << 31))
+    HY_REQUIRE(!f16 || n / 4 < (1LL << 31), HYRES_E_SHAPE, "se_fwd: too large for fp16");
+    if (f16)
+        hipLaunchKernelGGL(se_scale4_kernel<true>, dim3(pw_grid(n / 4)), dim3(256), 0, st, x, (const float*)sgate, y, B,
+                           HW, C);
+    else if (C % 4 == 0 && aligned16(x) && aligned16(y) && n / 4 < (1LL << 31))
         hipLaunchKernelGGL(se_scale4_kernel<false>, dim3(pw_grid(n / 4)), dim3(256), 0, st, x, (const float*)sgate, y, B,
                            HW, C);
     else
         hipLaunchKernelGGL(se_scale_kernel, dim3(grid_for_r(n)), dim3(256), 0, st, x, (const float*)sgate, y, B, HW, C);
     return HY_LAUNCH_CHECK("se_scale");
-}
-
-int hyres_se_fwd_f16(const void* x, const float* w1, const float* w2, void* y, float* pooled, float* hidden,
-                     float* sgate, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, hyres_stream_t s) {
-    HY_REQUIRE(x && w1 && w2 && y && pooled && hidden && sgate, HYRES_E_ARG, "se_fwd_f16: NULL");
-    HY_REQUIRE(C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(y) & 7) == 0,
-               HYRES_E_ALIGN, "se_fwd_f16: C %% 4 == 0, 256 %% (C/4) == 0, 8B-aligned x/y required");
-    const int nch = se_chunks(HW);
-    HY_REQUIRE(ws && ws_bytes >= (long long)B * nch * C * 4, HYRES_E_WORKSPACE, "se_fwd_f16: workspace");
-    const int per = (HW + nch - 1) / nch;
-    hipStream_t st = as_stream(s);
-    hipLaunchKernelGGL((se_pool4_kernel<false, true>), dim3(B, nch), dim3(256), 0, st, (const float*)x,
-                       (const float*)nullptr, HW, C, per, (float*)ws);
-    int rc = HY_LAUNCH_CHECK("se_pool_f16");
-    if (rc) return rc;
-    hipLaunchKernelGGL(se_fc_kernel, dim3(B), dim3(256), (C + Cr) * 4, st, (const float*)ws, nch, w1, w2, pooled,
-                       hidden, sgate, HW, C, Cr);
-    rc = HY_LAUNCH_CHECK("se_fc");
-    if (rc) return rc;
-    const long long n = (long long)B * HW * C / 4;
-    HY_REQUIRE(n < (1LL << 31), HYRES_E_SHAPE, "se_fwd_f16: too large");
-    hipLaunchKernelGGL(se_scale4_kernel<true>, dim3(pw_grid(n)), dim3(256), 0, st, (const float*)x, (const float*)sgate,
-                       (float*)y, B, HW, C);
-    return HY_LAUNCH_CHECK("se_scale_f16");
 }
 
 extern "C++" {
@@ -1105,44 +1089,28 @@ static int se_bwd_impl(const float* x, const float* gy, const float* w1, const f
     return HY_LAUNCH_CHECK("se_bwd_x");
 }
 }  // extern "C++"
-int hyres_se_bwd(const float* x, const float* gy, const float* w1, const float* w2, const float* pooled,
-                 const float* hidden, const float* sgate, float* gx, float* gw1, float* gw2, int B, int HW, int C,
-                 int Cr, void* ws, long long ws_bytes, hyres_stream_t s) {
-    return se_bwd_impl<false, false>(x, gy, w1, w2, pooled, hidden, sgate, gx, gw1, gw2, B, HW, C, Cr, ws, ws_bytes, s);
+int hyres_se_bwd(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
+                 const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW, int C,
+                 int Cr, void* ws, long long ws_bytes, int dt, hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "se_bwd");
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        return se_bwd_impl<H, G>((const float*)x, (const float*)gy, w1, w2, pooled, hidden, sgate, (float*)gx, gw1, gw2, B,
+                                 HW, C, Cr, ws, ws_bytes, s);
+    });
 }
-int hyres_se_bwd_prelu(const float* x, const float* gy, const float* w1, const float* w2, const float* pooled,
-                       const float* hidden, const float* sgate, float* gx, float* gw1, float* gw2, int B, int HW, int C,
-                       int Cr, const float* pre, const float* slope, float* dslope, void* ws, long long ws_bytes,
+int hyres_se_bwd_prelu(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
+                       const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW, int C,
+                       int Cr, const void* pre, const float* slope, float* dslope, void* ws, long long ws_bytes, int dt,
                        hyres_stream_t s) {
-    HY_REQUIRE(pre && slope && dslope && C % 4 == 0 && aligned16(gy) && aligned16(gx) && aligned16(pre) &&
+    HY_REQUIRE_DT(dt, "se_bwd_prelu");
+    const bool h = dt & HYRES_DT_ACT16, g16 = dt & HYRES_DT_GRAD16;
+    HY_REQUIRE(pre && slope && dslope && C % 4 == 0 && aligned_v4(gy, g16) && aligned_v4(gx, g16) && aligned_v4(pre, h) &&
                    (long long)B * HW * C / 4 < (1LL << 31),
-               HYRES_E_ARG, "se_bwd_prelu: needs pre / slope / dslope, C %% 4 == 0, 16B-aligned gy / gx / pre");
-    return se_bwd_impl<false, false>(x, gy, w1, w2, pooled, hidden, sgate, gx, gw1, gw2, B, HW, C, Cr, ws, ws_bytes, s,
-                                     pre, slope, dslope);
-}
-int hyres_se_bwd_prelu_f16(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
-                           const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW, int C,
-                           int Cr, const void* pre, const float* slope, float* dslope, void* ws, long long ws_bytes,
-                           int g16, hyres_stream_t s) {
-    const unsigned ag = g16 ? 7u : 15u;
-    HY_REQUIRE(pre && slope && dslope && C % 4 == 0 && (reinterpret_cast<uintptr_t>(gy) & ag) == 0 &&
-                   (reinterpret_cast<uintptr_t>(gx) & ag) == 0 && (reinterpret_cast<uintptr_t>(pre) & 7u) == 0 &&
-                   (long long)B * HW * C / 4 < (1LL << 31),
-               HYRES_E_ARG, "se_bwd_prelu_f16: needs pre / slope / dslope, C %% 4 == 0, aligned gy / gx / pre");
-    if (g16)
-        return se_bwd_impl<true, true>((const float*)x, (const float*)gy, w1, w2, pooled, hidden, sgate, (float*)gx, gw1,
-                                       gw2, B, HW, C, Cr, ws, ws_bytes, s, (const float*)pre, slope, dslope);
-    return se_bwd_impl<true, false>((const float*)x, (const float*)gy, w1, w2, pooled, hidden, sgate, (float*)gx, gw1,
-                                    gw2, B, HW, C, Cr, ws, ws_bytes, s, (const float*)pre, slope, dslope);
-}
-int hyres_se_bwd_f16(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
-                     const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW, int C,
-                     int Cr, void* ws, long long ws_bytes, int g16, hyres_stream_t s) {
-    if (g16)
-        return se_bwd_impl<true, true>((const float*)x, (const float*)gy, w1, w2, pooled, hidden, sgate, (float*)gx, gw1,
-                                       gw2, B, HW, C, Cr, ws, ws_bytes, s);
-    return se_bwd_impl<true, false>((const float*)x, (const float*)gy, w1, w2, pooled, hidden, sgate, (float*)gx, gw1,
-                                    gw2, B, HW, C, Cr, ws, ws_bytes, s);
+               HYRES_E_ARG, "se_bwd_prelu: needs pre / slope / dslope, C %% 4 == 0, aligned gy / gx / pre");
+    return dispatch_hg(dt, [&](auto H, auto G) {
+        return se_bwd_impl<H, G>((const float*)x, (const float*)gy, w1, w2, pooled, hidden, sgate, (float*)gx, gw1, gw2, B,
+                                 HW, C, Cr, ws, ws_bytes, s, (const float*)pre, slope, dslope);
+    });
 }
 
 static int sa_bwd_blocks(long long n) {  // >= 4 pixels per thread: the 98-tap weight fold is amortised
@@ -1159,20 +1127,20 @@ long long hyres_spatial_attn_workspace_bytes(int B, int H, int W) {
     return nb * 98 * 4 + n * 4 + n * 2 * 4 + 1024;
 }
 
-int hyres_spatial_attn_fwd(const float* x, const float* w, float* pooled2, int* argmax, float* attn, float* y, int B,
-                           int H, int W, int C, hyres_stream_t s) {
+extern "C++" {
+template <bool HF>
+static int spatial_attn_fwd_impl(const float* x, const float* w, float* pooled2, int* argmax, float* attn, float* y, int B,
+                                 int H, int W, int C, hyres_stream_t s) {
     HY_REQUIRE(x && w && pooled2 && argmax && attn, HYRES_E_ARG, "spatial_attn_fwd: NULL");  // y NULL: map only
-    HY_REQUIRE(C % 4 == 0 && C <= 1024 && aligned16(x) && (!y || aligned16(y)), HYRES_E_ALIGN,
-               "spatial_attn: C %% 4 == 0 and 16B-aligned x/y required");
-    long long P = (long long)B * H * W;
+    HY_REQUIRE(C % 4 == 0 && C <= 1024 && aligned_v4(x, HF) && aligned_v4(y, HF), HYRES_E_ALIGN,
+               "spatial_attn_fwd: C %% 4 == 0 and aligned x/y (8 B fp16, 16 B fp32) required");
+    const long long P = (long long)B * H * W;
     hipStream_t st = as_stream(s);
-    HY_REQUIRE(C % 4 == 0 && aligned16(x), HYRES_E_ALIGN, "spatial_attn_fwd: C %% 4 and 16B-aligned x needed");
     if (C == 192)
-        hipLaunchKernelGGL((sa_pool_kernel<false, 3>), dim3((unsigned)((P + 15) / 16)), dim3(256), 0, st, x, pooled2, argmax,
+        hipLaunchKernelGGL((sa_pool_kernel<HF, 3>), dim3((unsigned)((P + 15) / 16)), dim3(256), 0, st, x, pooled2, argmax,
                            P, C);
     else
-        hipLaunchKernelGGL(sa_pool_kernel<false>, dim3((unsigned)((P + 15) / 16)), dim3(256), 0, st, x, pooled2, argmax, P,
-                           C);
+        hipLaunchKernelGGL(sa_pool_kernel<HF>, dim3((unsigned)((P + 15) / 16)), dim3(256), 0, st, x, pooled2, argmax, P, C);
     int rc = HY_LAUNCH_CHECK("sa_pool");
     if (rc) return rc;
     hipLaunchKernelGGL(sa_conv_tiled_kernel, dim3((unsigned)sa_tiles(B, H, W)), dim3(256), 0, st, (const float*)pooled2,
@@ -1180,34 +1148,15 @@ int hyres_spatial_attn_fwd(const float* x, const float* w, float* pooled2, int* 
     rc = HY_LAUNCH_CHECK("sa_conv");
     if (rc) return rc;
     if (!y) return ok();  // the attention map only (the multiply folded into the consumer: HYRES_EPI_ROWSCALE)
-    hipLaunchKernelGGL(sa_mul_kernel<false>, dim3(grid_for_r(P * C / 4)), dim3(256), 0, st, x, (const float*)attn, y, P, C);
+    hipLaunchKernelGGL(sa_mul_kernel<HF>, dim3(grid_for_r(P * C / 4)), dim3(256), 0, st, x, (const float*)attn, y, P, C);
     return HY_LAUNCH_CHECK("sa_mul");
 }
-
-int hyres_spatial_attn_fwd_f16(const void* x, const float* w, float* pooled2, int* argmax, float* attn, void* y, int B,
-                               int H, int W, int C, hyres_stream_t s) {
-    HY_REQUIRE(x && w && pooled2 && argmax && attn, HYRES_E_ARG, "spatial_attn_fwd_f16: NULL");  // y NULL: map only
-    HY_REQUIRE(C % 4 == 0 && C <= 1024 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(y) & 7) == 0,
-               HYRES_E_ALIGN, "spatial_attn_fwd_f16: C %% 4 == 0 and 8B-aligned x/y required");
-    const long long P = (long long)B * H * W;
-    hipStream_t st = as_stream(s);
-    if (C == 192)
-        hipLaunchKernelGGL((sa_pool_kernel<true, 3>), dim3((unsigned)((P + 15) / 16)), dim3(256), 0, st, (const float*)x,
-                           pooled2, argmax, P, C);
-    else
-        hipLaunchKernelGGL(sa_pool_kernel<true>, dim3((unsigned)((P + 15) / 16)), dim3(256), 0, st, (const float*)x,
-                           pooled2, argmax, P, C);
-    int rc = HY_LAUNCH_CHECK("sa_pool_f16");
-    if (rc) return rc;
-    hipLaunchKernelGGL(sa_conv_tiled_kernel, dim3((unsigned)sa_tiles(B, H, W)), dim3(256), 0, st, (const float*)pooled2,
-                       w, attn, B, H, W);
-    rc = HY_LAUNCH_CHECK("sa_conv");
-    if (rc) return rc;
-    if (!y) return ok();  // the attention map only
-    hipLaunchKernelGGL(sa_mul_kernel<true>, dim3(grid_for_r(P * C / 4)), dim3(256), 0, st, (const float*)x,
-                       (const float*)attn, (float*)y, P, C);
-    return HY_LAUNCH_CHECK("sa_mul_f16");
+}  // extern "C++"
+int hyres_spatial_attn_fwd(const void* x, const float* w, float* pooled2, int* argmax, float* attn, void* y, int B, int H,
+                           int W, int C, int f16, hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "spatial_attn_fwd");
+    if (f16) return spatial_attn_fwd_impl<true>((const float*)x, w, pooled2, argmax, attn, (float*)y, B, H, W, C, s);
+    return spatial_attn_fwd_impl<false>((const float*)x, w, pooled2, argmax, attn, (float*)y, B, H, W, C, s);
 }
 
 extern "C++" {
@@ -1248,43 +1197,32 @@ static int sa_fold_blocks(long long P) { return (int)std::max<long long>(1, std:
 
 long long hyres_sa_fold_workspace_bytes(long long P, int C) { return (long long)sa_fold_blocks(P) * (C + 1) * 4 + 256; }
 
-int hyres_sa_fold_bwd(const float* pre, int ldpre, const float* gy, int ldg, const float* attn, const float* bias,
-                      const float* slope, float* gs, float* glogit, float* dbias, float* dslope, long long P, int C,
-                      void* ws, long long ws_bytes, hyres_stream_t s) {
+int hyres_sa_fold_bwd(const void* prev, int ldpre, const void* gyv, int ldg, const float* attn, const float* bias,
+                      const float* slope, void* gsv, float* glogit, float* dbias, float* dslope, long long P, int C,
+                      void* ws, long long ws_bytes, int dt, hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "sa_fold_bwd");
+    const float *pre = (const float*)prev, *gy = (const float*)gyv;
+    float* gs = (float*)gsv;
     HY_REQUIRE(pre && gy && attn && bias && slope && gs && glogit && dbias && dslope && P > 0, HYRES_E_ARG,
                "sa_fold_bwd: NULL");
-    HY_REQUIRE(C % 4 == 0 && C > 0 && C <= 64 && ldpre % 4 == 0 && ldg % 4 == 0 && aligned16(pre) && aligned16(gy) &&
-                   aligned16(gs) && aligned16(bias),
-               HYRES_E_ALIGN, "sa_fold_bwd: C %% 4 == 0, C <= 64, 16B-aligned rows");
+    const bool h = dt & HYRES_DT_ACT16;  // fp16 pre: 8-channel vectors; fp32: 4-channel vectors and bias read as float4
+    const int v = h ? 8 : 4;
+    HY_REQUIRE(C % v == 0 && C > 0 && C <= 64 && ldpre % v == 0 && ldg % v == 0 && aligned16(pre) && aligned16(gy) &&
+                   aligned16(gs) && (h || aligned16(bias)),
+               HYRES_E_ALIGN, "sa_fold_bwd: C %% 4 == 0 (fp16: %% 8), C <= 64, 16B-aligned rows");
     HY_REQUIRE(ws && ws_bytes >= hyres_sa_fold_workspace_bytes(P, C), HYRES_E_WORKSPACE, "sa_fold_bwd: workspace");
     const int nb = sa_fold_blocks(P);
     hipStream_t st = as_stream(s);
-    hipLaunchKernelGGL(sa_fold_bwd_kernel, dim3(nb), dim3(256), 0, st, pre, ldpre, gy, ldg, attn, bias, slope, gs, glogit,
-                       (float*)ws, P, C);
-    int rc = HY_LAUNCH_CHECK("sa_fold_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL(sa_fold_final_kernel, dim3(C + 1), dim3(256), 0, st, (const float*)ws, nb, C, dbias, dslope);
-    return HY_LAUNCH_CHECK("sa_fold_final");
-}
-
-int hyres_sa_fold_bwd_f16(const void* pre, int ldpre, const void* gy, int ldg, const float* attn, const float* bias,
-                          const float* slope, void* gs, float* glogit, float* dbias, float* dslope, long long P, int C,
-                          void* ws, long long ws_bytes, int g16, hyres_stream_t s) {
-    HY_REQUIRE(pre && gy && attn && bias && slope && gs && glogit && dbias && dslope && P > 0, HYRES_E_ARG,
-               "sa_fold_bwd_f16: NULL");
-    HY_REQUIRE(C % 8 == 0 && C > 0 && C <= 64 && ldpre % 8 == 0 && ldg % 8 == 0 && aligned16(pre) && aligned16(gy) &&
-                   aligned16(gs),
-               HYRES_E_ALIGN, "sa_fold_bwd_f16: C %% 8 == 0, C <= 64, 16B-aligned rows");
-    HY_REQUIRE(ws && ws_bytes >= hyres_sa_fold_workspace_bytes(P, C), HYRES_E_WORKSPACE, "sa_fold_bwd_f16: workspace");
-    const int nb = sa_fold_blocks(P);
-    hipStream_t st = as_stream(s);
-    if (g16)
-        hipLaunchKernelGGL(sa_fold_bwd_h8_kernel<true>, dim3(nb), dim3(256), 0, st, (const float*)pre, ldpre,
-                           (const float*)gy, ldg, attn, bias, slope, (float*)gs, glogit, (float*)ws, P, C);
+    if (dt & HYRES_DT_GRAD16)
+        hipLaunchKernelGGL(sa_fold_bwd_h8_kernel<true>, dim3(nb), dim3(256), 0, st, pre, ldpre, gy, ldg, attn, bias, slope,
+                           gs, glogit, (float*)ws, P, C);
+    else if (h)
+        hipLaunchKernelGGL(sa_fold_bwd_h8_kernel<false>, dim3(nb), dim3(256), 0, st, pre, ldpre, gy, ldg, attn, bias, slope,
+                           gs, glogit, (float*)ws, P, C);
     else
-        hipLaunchKernelGGL(sa_fold_bwd_h8_kernel<false>, dim3(nb), dim3(256), 0, st, (const float*)pre, ldpre,
-                           (const float*)gy, ldg, attn, bias, slope, (float*)gs, glogit, (float*)ws, P, C);
-    int rc = HY_LAUNCH_CHECK("sa_fold_bwd_f16");
+        hipLaunchKernelGGL(sa_fold_bwd_kernel, dim3(nb), dim3(256), 0, st, pre, ldpre, gy, ldg, attn, bias, slope, gs,
+                           glogit, (float*)ws, P, C);
+    int rc = HY_LAUNCH_CHECK("sa_fold_bwd");
     if (rc) return rc;
     hipLaunchKernelGGL(sa_fold_final_kernel, dim3(C + 1), dim3(256), 0, st, (const float*)ws, nb, C, dbias, dslope);
     return HY_LAUNCH_CHECK("sa_fold_final");
@@ -1308,19 +1246,14 @@ int hyres_spatial_attn_bwd_map(const float* glogit, const float* pooled2, const 
     return HY_LAUNCH_CHECK("sa_bwd_wfinal");
 }
 
-int hyres_spatial_attn_bwd(const float* x, const float* w, const float* pooled2, const int* argmax, const float* attn,
-                           const float* gy, float* gx, float* gw, int B, int H, int W, int C, void* ws,
-                           long long ws_bytes, hyres_stream_t s) {
-    return spatial_attn_bwd_impl<false, false>(x, w, pooled2, argmax, attn, gy, gx, gw, B, H, W, C, ws, ws_bytes, s);
-}
-int hyres_spatial_attn_bwd_f16(const void* x, const float* w, const float* pooled2, const int* argmax,
-                               const float* attn, const void* gy, void* gx, float* gw, int B, int H, int W, int C,
-                               void* ws, long long ws_bytes, int g16, hyres_stream_t s) {
-    if (g16)
-        return spatial_attn_bwd_impl<true, true>((const float*)x, w, pooled2, argmax, attn, (const float*)gy, (float*)gx,
-                                                 gw, B, H, W, C, ws, ws_bytes, s);
-    return spatial_attn_bwd_impl<true, false>((const float*)x, w, pooled2, argmax, attn, (const float*)gy, (float*)gx, gw,
-                                              B, H, W, C, ws, ws_bytes, s);
+int hyres_spatial_attn_bwd(const void* x, const float* w, const float* pooled2, const int* argmax, const float* attn,
+                           const void* gy, void* gx, float* gw, int B, int H, int W, int C, void* ws, long long ws_bytes,
+                           int dt, hyres_stream_t s) {
+    HY_REQUIRE_DT(dt, "spatial_attn_bwd");
+    return dispatch_hg(dt, [&](auto HF, auto G) {
+        return spatial_attn_bwd_impl<HF, G>((const float*)x, w, pooled2, argmax, attn, (const float*)gy, (float*)gx, gw, B,
+                                            H, W, C, ws, ws_bytes, s);
+    });
 }
 
 }  // extern "C"

@@ -2605,11 +2605,8 @@ static int wgrad_issue(const hyres_wgrad_desc* d0, const float* pp, const float*
     }
     if (dbias && r.swap) {  // P (= dY) is the tap-folded side here: plain column sums (own workspace after the slab)
         const int P = d0->B * d0->Hq * d0->Wq;
-        if (d0->io_f16 & 1)
-            return hyres_colsum_f16(p_orig, P, d0->M, d0->ldp, dbias, d0->accumulate, bias_ws,
-                                    hyres_colsum_workspace_bytes(P, d0->M), s);
         return hyres_colsum(p_orig, P, d0->M, d0->ldp, dbias, d0->accumulate, bias_ws,
-                            hyres_colsum_workspace_bytes(P, d0->M), s);
+                            hyres_colsum_workspace_bytes(P, d0->M), d0->io_f16 & 1, s);
     }
     return 0;
 }
@@ -2730,8 +2727,11 @@ static int colsum_blocks(int P) {
 
 long long hyres_colsum_workspace_bytes(int P, int C) { return (long long)colsum_blocks(P) * C * 4; }
 
-static int colsum_impl(const float* x, int P, int C, int ld, float* dst, int accumulate, void* ws, long long ws_bytes,
-                       bool h, hyres_stream_t s) {
+int hyres_colsum(const void* xv, int P, int C, int ld, float* dst, int accumulate, void* ws, long long ws_bytes, int f16,
+                 hyres_stream_t s) {
+    HY_REQUIRE_F16(f16, "colsum");
+    const float* x = (const float*)xv;
+    const bool h = f16;
     HY_REQUIRE(x && dst && P > 0 && C > 0, HYRES_E_ARG, "colsum: bad args");
     const int nb = colsum_blocks(P);
     const int rows = ceil_div(P, nb);
@@ -2761,15 +2761,6 @@ static int colsum_impl(const float* x, int P, int C, int ld, float* dst, int acc
         hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(ceil_div(C, 16)), dim3(256), 0, st, (const float*)ws, nb, 1, C,
                            1, dst, 1, 0, 0, accumulate);
     return HY_LAUNCH_CHECK("colsum_reduce");
-}
-
-int hyres_colsum(const float* x, int P, int C, int ld, float* dst, int accumulate, void* ws,
-                 long long ws_bytes, hyres_stream_t s) {
-    return colsum_impl(x, P, C, ld, dst, accumulate, ws, ws_bytes, false, s);
-}
-int hyres_colsum_f16(const void* x, int P, int C, int ld, float* dst, int accumulate, void* ws,
-                     long long ws_bytes, hyres_stream_t s) {
-    return colsum_impl((const float*)x, P, C, ld, dst, accumulate, ws, ws_bytes, true, s);
 }
 
 }  // extern "C"

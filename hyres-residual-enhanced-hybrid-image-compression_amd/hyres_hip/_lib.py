@@ -21,7 +21,8 @@ WPREP_CONV, WPREP_CONV_DGRAD, WPREP_DECONV, WPREP_DECONV_DGRAD = 0, 1, 2, 3
 EPI_BIAS, EPI_GDN, EPI_IGDN, EPI_GDN_BWD, EPI_IGDN_BWD, EPI_ROWSCALE, EPI_SA_BWD = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_RELU_MASK, ACT_PRELU_MASK = 0, 1, 2, 3, 4
 PRELU_PARTIALS = 2048  # HYRES_PRELU_PARTIALS
-IO_X16, IO_Y16, IO_AUX16 = 1, 2, 4  # hyres_epilogue.io_f16 bits (fp16 activations in HBM)
+IO_X16, IO_Y16, IO_AUX16 = 1, 2, 4  # hyres_epilogue.io_f16 bits (fp16 activations in HBM); X16 | Y16: hyres_add2d's io
+DT_ACT16, DT_GRAD16 = 1, 2  # HYRES_DT_*: the ``dt`` mask of the element-wise / MultiScaleRefine entry points
 EB_REC = 64
 
 
@@ -105,38 +106,27 @@ _SIGS = {
     "hyres_wgrad_reduce_jobs": (_I, [ctypes.POINTER(WgradJob), _I, _P]),
     "hyres_ru_fused_f16_ok": (_I, [_I, _I, _I, _I]),
     "hyres_ru_fused_f16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
-    "hyres_colsum": (_I, [_P, _I, _I, _I, _P, _I, _P, _LL, _P]),
+    "hyres_colsum": (_I, [_P, _I, _I, _I, _P, _I, _P, _LL, _I, _P]),
     "hyres_colsum_workspace_bytes": (_LL, [_I, _I]),
-    "hyres_colsum_f16": (_I, [_P, _I, _I, _I, _P, _I, _P, _LL, _P]),
     "hyres_nchw_to_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "hyres_nhwc_to_nchw": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     "hyres_axpby": (_I, [_P, _P, _F, _P, _LL, _P]),
     "hyres_add_clamp01": (_I, [_P, _P, _P, _LL, _P]),
     "hyres_add_clamp01_bwd": (_I, [_P, _P, _P, _I, _LL, _P]),
     "hyres_relu_bwd": (_I, [_P, _P, _P, _LL, _P]),
-    "hyres_relu_bwd_2d": (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _P]),
-    "hyres_prelu_bwd": (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _P, _P, _P, _LL, _P]),
-    "hyres_attn_gate_fwd": (_I, [_P, _P, _P, _P, _LL, _P]),
-    "hyres_attn_gate_fwd_f16": (_I, [_P, _P, _P, _P, _LL, _P]),
-    "hyres_attn_gate_bwd": (_I, [_P, _P, _P, _P, _P, _LL, _P]),
-    "hyres_attn_gate_bwd_relu": (_I, [_P, _P, _P, _P, _P, _LL, _P]),
-    "hyres_attn_gate_bwd_f16": (_I, [_P, _P, _P, _P, _P, _LL, _I, _P]),
-    "hyres_attn_gate_bwd_relu_f16": (_I, [_P, _P, _P, _P, _P, _LL, _I, _P]),
-    "hyres_relu_bwd_2d_f16": (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _I, _P]),
-    "hyres_prelu_bwd_f16": (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _P, _P, _P, _LL, _I, _P]),
-    "hyres_gdn_dnorm_f16": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _P]),
-    "hyres_se_bwd_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _I, _P]),
-    "hyres_spatial_attn_bwd_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _I, _P]),
-    "hyres_accumulate": (_I, [_P, _P, _LL, _P]),
-    "hyres_accumulate_f16": (_I, [_P, _P, _LL, _P]),
+    "hyres_relu_bwd_2d": (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _I, _P]),
+    "hyres_prelu_bwd": (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _P, _P, _P, _LL, _I, _P]),
+    "hyres_attn_gate_fwd": (_I, [_P, _P, _P, _P, _LL, _I, _P]),
+    "hyres_attn_gate_bwd": (_I, [_P, _P, _P, _P, _P, _LL, _I, _P]),
+    "hyres_attn_gate_bwd_relu": (_I, [_P, _P, _P, _P, _P, _LL, _I, _P]),
+    "hyres_accumulate": (_I, [_P, _P, _LL, _I, _P]),
     "hyres_scale": (_I, [_P, _P, _F, _P, _LL, _I, _P]),
-    "hyres_add2d": (_I, [_P, _I, _P, _I, _LL, _I, _I, _P]),
-    "hyres_add2d_f16": (_I, [_P, _I, _P, _I, _LL, _I, _I, _I, _P]),
+    "hyres_add2d": (_I, [_P, _I, _P, _I, _LL, _I, _I, _I, _P]),
     "hyres_mul": (_I, [_P, _P, _P, _LL, _P]),
     "hyres_zero": (_I, [_P, _LL, _P]),
     "hyres_gdn_reparam_fwd": (_I, [_P, _P, _P, _P, _I, _P]),
     "hyres_gdn_reparam_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    "hyres_gdn_dnorm": (_I, [_P, _P, _P, _P, _LL, _I, _I, _P]),
+    "hyres_gdn_dnorm": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _P]),
     "hyres_uniform_noise": (_I, [_P, _LL, _ULL, _ULL, _P]),
     "hyres_uniform_noise_dev": (_I, [_P, _LL, _P, _ULL, _P]),
     "hyres_quantize": (_I, [_P, _I, _P, _LL, _P]),
@@ -165,25 +155,19 @@ _SIGS = {
     "hyres_eb_workspace_bytes": (_LL, [_LL, _I]),
     "hyres_eb_unpack_grad": (_I, [_P, _I, _PP, _PP, _PP, _PP, _PP, _P, _I, _I, _P]),
     "hyres_eb_aux_loss": (_I, [_P, _P, _P, _P, _P, _I, _P]),
-    "hyres_bilinear_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
-    "hyres_bilinear_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
-    "hyres_bilinear_bwd_f16": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
+    "hyres_bilinear_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _P]),
+    "hyres_bilinear_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _P]),
     "hyres_bilinear_bwd_prelu_workspace_bytes": (_LL, [_I, _I, _I, _I]),
     "hyres_bilinear_bwd_prelu": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P, _LL, _I, _P]),
-    "hyres_se_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _P]),
-    "hyres_se_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _P]),
-    "hyres_se_bwd_prelu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P]),
-    "hyres_se_bwd_prelu_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _I, _P]),
+    "hyres_se_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _I, _P]),
+    "hyres_se_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _I, _P]),
+    "hyres_se_bwd_prelu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _I, _P]),
     "hyres_se_workspace_bytes": (_LL, [_I, _I, _I]),
-    "hyres_spatial_attn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "hyres_bilinear_fwd_f16": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
-    "hyres_se_fwd_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _P]),
-    "hyres_spatial_attn_fwd_f16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "hyres_spatial_attn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _P]),
+    "hyres_spatial_attn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "hyres_spatial_attn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _I, _P]),
     "hyres_spatial_attn_workspace_bytes": (_LL, [_I, _I, _I]),
     "hyres_sa_fold_workspace_bytes": (_LL, [_LL, _I]),
-    "hyres_sa_fold_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _P, _LL, _P]),
-    "hyres_sa_fold_bwd_f16": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _P, _LL, _I, _P]),
+    "hyres_sa_fold_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _P, _LL, _I, _P]),
     "hyres_spatial_attn_bwd_map": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _LL, _P]),
     "hyres_sum_log": (_I, [_P, _LL, _P, _P, _LL, _P]),
     "hyres_sum_sqdiff": (_I, [_P, _P, _LL, _P, _P, _LL, _P]),
@@ -264,6 +248,17 @@ def ptr(t) -> Optional[int]:
     if t is None:
         return None
     return t.data_ptr()
+
+
+def is_f16(t) -> bool:
+    """``t`` (a tensor, an ops.Node or None) is stored as fp16."""
+    return t is not None and getattr(t, "v", t).dtype == torch.float16
+
+
+def dt_mask(act=None, grad=None, a: int = DT_ACT16, g: int = DT_GRAD16) -> int:
+    """``a`` if ``act`` is fp16, or-ed with ``g`` if ``grad`` is: the ``dt`` argument (saved activation, gradient) by
+    default; with other bits the X / Y / AUX and P / Q masks of the conv and weight-gradient descriptors."""
+    return (a if is_f16(act) else 0) | (g if is_f16(grad) else 0)
 
 
 def ptr_array(ts):

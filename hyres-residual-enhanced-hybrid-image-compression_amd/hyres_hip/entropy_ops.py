@@ -102,7 +102,7 @@ def entropy_bottleneck(tape: Optional[Tape], eb, z: Node, training: bool, noiseq
         L.call("hyres_eb_bwd", z_q.data_ptr(), packed.data_ptr(), lik.ptr(), L.ptr(g_lik), L.ptr(g_zh),
                int(training), int(noisequant), gz.data_ptr(), ws.data_ptr(), P, C, L.stream())
         if acc:
-            L.call("hyres_accumulate", gz.data_ptr(), tgt.data_ptr(), gz.numel(), L.stream())
+            L.call("hyres_accumulate", gz.data_ptr(), tgt.data_ptr(), gz.numel(), 0, L.stream())
         if any(p.requires_grad for p in mats + biases + factors):
             nb = (P + 1023) // 1024
             gm = [param_grad(p) for p in mats]

@@ -258,18 +258,14 @@ class Node:
 
 def add2d(x: torch.Tensor, ldx: int, y: torch.Tensor, ldy: int, P: int, C: int, acc: int) -> None:
     """y[p, c] (+)= x[p, c] over [P][C] with pixel strides ldx / ldy, each side fp32 or fp16 (its tensor's dtype)."""
-    io = (1 if x.dtype == torch.float16 else 0) | (2 if y.dtype == torch.float16 else 0)
-    if io:
-        L.call("hyres_add2d_f16", x.data_ptr(), ldx, y.data_ptr(), ldy, P, C, acc, io, L.stream())
-    else:
-        L.call("hyres_add2d", x.data_ptr(), ldx, y.data_ptr(), ldy, P, C, acc, L.stream())
+    L.call("hyres_add2d", x.data_ptr(), ldx, y.data_ptr(), ldy, P, C, acc, L.dt_mask(x, y, L.IO_X16, L.IO_Y16),
+           L.stream())
 
 
 def accumulate(x: torch.Tensor, y: torch.Tensor) -> None:
     """y += x elementwise (same dtype)."""
     assert x.dtype == y.dtype
-    fn = "hyres_accumulate_f16" if x.dtype == torch.float16 else "hyres_accumulate"
-    L.call(fn, x.data_ptr(), y.data_ptr(), x.numel(), L.stream())
+    L.call("hyres_accumulate", x.data_ptr(), y.data_ptr(), x.numel(), int(L.is_f16(x)), L.stream())
 
 
 class Tape:
@@ -674,7 +670,7 @@ def act_f16(tape: Optional["Tape"], H: int, W: int) -> bool:
 
 
 def _io_flags(x: "Node", y: "Node", tape: Optional["Tape"]) -> int:
-    return (L.IO_X16 if x.half else 0) | (L.IO_Y16 if y.half else 0)
+    return L.dt_mask(x, y, L.IO_X16, L.IO_Y16)
 
 
 def _launch_conv(g: L.ConvGeom, x_ptr: int, w2: torch.Tensor, ldw: int, y_ptr: int, e: L.Epilogue) -> None:
@@ -700,17 +696,14 @@ def _launch_conv(g: L.ConvGeom, x_ptr: int, w2: torch.Tensor, ldw: int, y_ptr: i
 
 def _colsum_into(g: torch.Tensor, P: int, C: int, ld: int, dst: torch.Tensor, acc: int = 1) -> None:
     ws = _ws(L.load().hyres_colsum_workspace_bytes(P, C), g.device, slot=1)
-    fn = "hyres_colsum_f16" if g.dtype == torch.float16 else "hyres_colsum"
-    L.call(fn, g.data_ptr(), P, C, ld, dst.data_ptr(), acc, ws.data_ptr(), ws.numel(), L.stream())
+    L.call("hyres_colsum", g.data_ptr(), P, C, ld, dst.data_ptr(), acc, ws.data_ptr(), ws.numel(), int(L.is_f16(g)),
+           L.stream())
 
 
 def _dgrad_io(gp: torch.Tensor, x: "Node") -> int:
     """io_f16 of an input-gradient conv: X = the incoming gradient ``gp``, Y = x's gradient, the ReLU mask (x's
     values) fp16 with Y or alone (AUX16: fp16 activation, fp32 gradient)."""
-    io = (L.IO_X16 if gp.dtype == torch.float16 else 0) | (L.IO_Y16 if x.ghalf else 0)
-    if x.half and not x.ghalf:
-        io |= L.IO_AUX16
-    return io
+    return L.dt_mask(gp, x, L.IO_X16, L.IO_Y16 if x.ghalf else L.IO_AUX16)
 
 
 class SideStream:
@@ -879,22 +872,14 @@ def _act_backward(y: Node, gy: torch.Tensor, gy_ld: int, act: int, pre: Optional
     if act == L.ACT_NONE or (act == L.ACT_RELU and y.gmasked) or (act == L.ACT_PRELU and y.pmasked):
         return gy, gy_ld
     gp = _empty((y.B, y.H, y.W, y.C), y.device, gy.dtype)
-    g16 = int(gy.dtype == torch.float16)
     if act == L.ACT_RELU:
-        if y.half:
-            L.call("hyres_relu_bwd_2d_f16", y.ptr(), y.ld, gy.data_ptr(), gy_ld, gp.data_ptr(), y.C, y.P, y.C, g16,
-                   L.stream())
-        else:
-            L.call("hyres_relu_bwd_2d", y.ptr(), y.ld, gy.data_ptr(), gy_ld, gp.data_ptr(), y.C, y.P, y.C, L.stream())
+        L.call("hyres_relu_bwd_2d", y.ptr(), y.ld, gy.data_ptr(), gy_ld, gp.data_ptr(), y.C, y.P, y.C, L.dt_mask(y, gy),
+               L.stream())
     else:
         ws = _ws(L.load().hyres_reduce_workspace_bytes(y.P * y.C), y.device, slot=1)
         dslope = param_grad(slope) if slope.requires_grad else _empty((1,), y.device)
-        if pre.dtype == torch.float16:
-            L.call("hyres_prelu_bwd_f16", pre.data_ptr(), y.C, gy.data_ptr(), gy_ld, gp.data_ptr(), y.C, y.P, y.C,
-                   slope.data_ptr(), dslope.data_ptr(), ws.data_ptr(), ws.numel(), g16, L.stream())
-        else:
-            L.call("hyres_prelu_bwd", pre.data_ptr(), y.C, gy.data_ptr(), gy_ld, gp.data_ptr(), y.C, y.P, y.C,
-                   slope.data_ptr(), dslope.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+        L.call("hyres_prelu_bwd", pre.data_ptr(), y.C, gy.data_ptr(), gy_ld, gp.data_ptr(), y.C, y.P, y.C,
+               slope.data_ptr(), dslope.data_ptr(), ws.data_ptr(), ws.numel(), L.dt_mask(pre, gy), L.stream())
     return gp, y.C
 
 
@@ -985,7 +970,7 @@ def conv2d(tape: Optional[Tape], x: Node, weight: torch.Tensor, bias: Optional[t
             d.accumulate = 1
             d.f16_operands = f16 * AMP_WGRAD_F16
             # P = the (fp16 under AMP) gradient, Q = the saved input activation
-            d.io_f16 = (1 if gp.dtype == torch.float16 else 0) | (2 if x.half else 0)
+            d.io_f16 = L.dt_mask(gp, x, 1, 2)
             _wgrad(d, gp.data_ptr(), x.ptr(), param_grad(weight), x.device,
                    param_grad(bias) if wants_grad(bias) else None, keep=(gp, x.v), side=True)
         if x.rg:
@@ -1045,7 +1030,7 @@ def deconv2d(tape: Optional[Tape], x: Node, weight: torch.Tensor, bias: Optional
             d.accumulate = 1
             d.f16_operands = f16 * AMP_WGRAD_F16
             # P = the saved input activation, Q = the (fp16 under AMP) gradient
-            d.io_f16 = (1 if x.half else 0) | (2 if gp.dtype == torch.float16 else 0)
+            d.io_f16 = L.dt_mask(x, gp, 1, 2)
             _wgrad(d, x.ptr(), gp.data_ptr(), param_grad(weight), x.device, keep=(gp, x.v), side=True)
         if x.rg:
             ed = L.Epilogue()
@@ -1104,12 +1089,8 @@ def gdn(tape: Optional[Tape], x: Node, beta: torch.Tensor, gamma: torch.Tensor, 
             add2d(gy, gld, t, C, y.P, C, 0)
             gy = t
         dn = _empty((x.B, x.H, x.W, C), dev, gy.dtype)  # the norm's gradient: fp16 with y's (AMP)
-        if y.half:
-            L.call("hyres_gdn_dnorm_f16", gy.data_ptr(), y.ptr(), nrm.data_ptr(), dn.data_ptr(), y.P, C, int(inverse),
-                   int(gy.dtype == torch.float16), L.stream())
-        else:
-            L.call("hyres_gdn_dnorm", gy.data_ptr(), y.ptr(), nrm.data_ptr(), dn.data_ptr(), y.P, C, int(inverse),
-                   L.stream())
+        L.call("hyres_gdn_dnorm", gy.data_ptr(), y.ptr(), nrm.data_ptr(), dn.data_ptr(), y.P, C, int(inverse),
+               L.dt_mask(y, gy), L.stream())
         if beta.requires_grad or gamma.requires_grad:
             dgp = _empty((C, C), dev)
             d = L.WgradDesc()
@@ -1117,7 +1098,7 @@ def gdn(tape: Optional[Tape], x: Node, beta: torch.Tensor, gamma: torch.Tensor, 
             d.square_q = 1
             d.accumulate = 0
             d.f16_operands = f16 * AMP_WGRAD_F16
-            d.io_f16 = (1 if dn.dtype == torch.float16 else 0) | (2 if x.half else 0)
+            d.io_f16 = L.dt_mask(dn, x, 1, 2)
             _wgrad(d, dn.data_ptr(), x.ptr(), dgp, dev, defer=False)  # read by the reparam backward below
             dbp = _empty((C,), dev)
             _colsum_into(dn, y.P, C, C, dbp, acc=0)
@@ -1186,9 +1167,7 @@ def attn_gate(tape: Optional[Tape], a: Node, b: Node, x: Node) -> Node:
     out = Node.new(a.B, a.H, a.W, a.C, a.device, dtype=a.v.dtype)
     if a.half:
         assert b.half and x.half
-        L.call("hyres_attn_gate_fwd_f16", a.ptr(), b.ptr(), x.ptr(), out.ptr(), n, L.stream())
-    else:
-        L.call("hyres_attn_gate_fwd", a.ptr(), b.ptr(), x.ptr(), out.ptr(), n, L.stream())
+    L.call("hyres_attn_gate_fwd", a.ptr(), b.ptr(), x.ptr(), out.ptr(), n, int(a.half), L.stream())
     if tape is None:
         return out
 
@@ -1199,23 +1178,13 @@ def attn_gate(tape: Optional[Tape], a: Node, b: Node, x: Node) -> Node:
         ga, acc_a = a.grad_target()
         gb, acc_b = b.grad_target()
         assert acc_a == 0 and acc_b == 0, "gate inputs are single-consumer"
-        if a.half:
-            assert ga.dtype == gb.dtype == g.dtype
-            g16 = int(g.dtype == torch.float16)
-            if a.relu_out and a.parent is None and n % 4 == 0:  # the ReLU backward folded in, as below
-                L.call("hyres_attn_gate_bwd_relu_f16", a.ptr(), b.ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), n,
-                       g16, L.stream())
-                a.gmasked = True
-            else:
-                L.call("hyres_attn_gate_bwd_f16", a.ptr(), b.ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), n, g16,
-                       L.stream())
-        elif a.relu_out and a.parent is None and n % 4 == 0:
-            # the last ResidualUnit's ReLU backward folded in: a's gradient leaves here masked (its producer skips it)
-            L.call("hyres_attn_gate_bwd_relu", a.ptr(), b.ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), n,
-                   L.stream())
+        assert ga.dtype == gb.dtype == g.dtype
+        # the last ResidualUnit's ReLU backward folded in: a's gradient leaves here masked (its producer skips it)
+        fold = a.relu_out and a.parent is None and n % 4 == 0
+        L.call("hyres_attn_gate_bwd_relu" if fold else "hyres_attn_gate_bwd", a.ptr(), b.ptr(), g.data_ptr(),
+               ga.data_ptr(), gb.data_ptr(), n, L.dt_mask(a, g), L.stream())
+        if fold:
             a.gmasked = True
-        else:
-            L.call("hyres_attn_gate_bwd", a.ptr(), b.ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), n, L.stream())
         if x.rg:
             x.set_grad(g)
 

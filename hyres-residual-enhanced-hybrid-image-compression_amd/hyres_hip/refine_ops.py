@@ -23,11 +23,8 @@ def bilinear(tape: Optional[Tape], x: Node, Ho: int, Wo: int, scale_h: float, sc
     y = out if out is not None else Node.new(x.B, Ho, Wo, x.C, x.device, dtype=x.v.dtype)
     if x.half:  # fp16 activations (autocast; the backward below only reads gradients)
         assert y.half
-        L.call("hyres_bilinear_fwd_f16", x.ptr(), x.ld, y.ptr(), y.ld, x.B, x.H, x.W, Ho, Wo, x.C, float(scale_h),
-               float(scale_w), L.stream())
-    else:
-        L.call("hyres_bilinear_fwd", x.ptr(), x.ld, y.ptr(), y.ld, x.B, x.H, x.W, Ho, Wo, x.C, float(scale_h),
-               float(scale_w), 0, L.stream())
+    L.call("hyres_bilinear_fwd", x.ptr(), x.ld, y.ptr(), y.ld, x.B, x.H, x.W, Ho, Wo, x.C, float(scale_h),
+           float(scale_w), 0, int(x.half), L.stream())
     if tape is None:
         return y
 
@@ -44,15 +41,13 @@ def bilinear(tape: Optional[Tape], x: Node, Ho: int, Wo: int, scale_h: float, sc
             pre, slope = x.prelu
             dslope = param_grad(slope) if slope.requires_grad else _empty((1,), x.device)
             ws = _ws(L.load().hyres_bilinear_bwd_prelu_workspace_bytes(x.B, x.H, x.W, x.C), x.device, slot=1)
-            io = (1 if g.dtype == torch.float16 else 0) | (2 if pre.dtype == torch.float16 else 0)
             L.call("hyres_bilinear_bwd_prelu", g.data_ptr(), y.grad_ld(), tgt.data_ptr(), x.grad_ld(), x.B, x.H, x.W,
                    Ho, Wo, x.C, float(scale_h), float(scale_w), pre.data_ptr(), x.C, slope.data_ptr(),
-                   dslope.data_ptr(), ws.data_ptr(), ws.numel(), io, L.stream())
+                   dslope.data_ptr(), ws.data_ptr(), ws.numel(), L.dt_mask(pre, g), L.stream())
             x.pmasked = True
             return
-        fn = "hyres_bilinear_bwd_f16" if g.dtype == torch.float16 else "hyres_bilinear_bwd"  # AMP fp16 gradients
-        L.call(fn, g.data_ptr(), y.grad_ld(), tgt.data_ptr(), x.grad_ld(), x.B, x.H, x.W, Ho, Wo,
-               x.C, float(scale_h), float(scale_w), acc, L.stream())
+        L.call("hyres_bilinear_bwd", g.data_ptr(), y.grad_ld(), tgt.data_ptr(), x.grad_ld(), x.B, x.H, x.W, Ho, Wo,
+               x.C, float(scale_h), float(scale_w), acc, int(L.is_f16(g)), L.stream())  # AMP: fp16 gradients
 
     tape.push(bwd)
     return y
@@ -70,9 +65,8 @@ def se_block(tape: Optional[Tape], x: Node, w1: torch.Tensor, w2: torch.Tensor) 
     sgate = _empty((B, C), dev)
     wsb = L.load().hyres_se_workspace_bytes(B, HW, C)
     ws = _ws(wsb + B * C * 4, dev, slot=1)
-    fn = "hyres_se_fwd_f16" if x.half else "hyres_se_fwd"
-    L.call(fn, x.ptr(), w1.data_ptr(), w2.data_ptr(), y.ptr(), pooled.data_ptr(), hidden.data_ptr(),
-           sgate.data_ptr(), B, HW, C, Cr, ws.data_ptr(), ws.numel(), L.stream())
+    L.call("hyres_se_fwd", x.ptr(), w1.data_ptr(), w2.data_ptr(), y.ptr(), pooled.data_ptr(), hidden.data_ptr(),
+           sgate.data_ptr(), B, HW, C, Cr, ws.data_ptr(), ws.numel(), int(x.half), L.stream())
     if tape is None:
         return y
 
@@ -93,28 +87,18 @@ def se_block(tape: Optional[Tape], x: Node, w1: torch.Tensor, w2: torch.Tensor) 
             pre, slope = x.prelu
             dslope = param_grad(slope) if slope.requires_grad else _empty((1,), dev)
             ws2 = _ws(wsb + B * C * 4 + 2048 * 4, dev, slot=1)
-            if x.half:  # AMP (round 6): fp16 pre-activation, fp16 or fp32 gradients
-                L.call("hyres_se_bwd_prelu_f16", x.ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
-                       hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, HW, C, Cr,
-                       pre.data_ptr(), slope.data_ptr(), dslope.data_ptr(), ws2.data_ptr(), ws2.numel(),
-                       int(g.dtype == torch.float16), L.stream())
-            else:
-                assert g.dtype == torch.float32
-                L.call("hyres_se_bwd_prelu", x.ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
-                       hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, HW, C,
-                       Cr, pre.data_ptr(), slope.data_ptr(), dslope.data_ptr(), ws2.data_ptr(), ws2.numel(),
-                       L.stream())
+            # (AMP, round 6: fp16 x and pre-activation, fp16 or fp32 gradients)
+            assert x.half or g.dtype == torch.float32
+            L.call("hyres_se_bwd_prelu", x.ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
+                   hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, HW, C, Cr,
+                   pre.data_ptr(), slope.data_ptr(), dslope.data_ptr(), ws2.data_ptr(), ws2.numel(), L.dt_mask(x, g),
+                   L.stream())
             x.pmasked = True
             return
         ws2 = _ws(wsb + B * C * 4, dev, slot=1)
-        if x.half:
-            L.call("hyres_se_bwd_f16", x.ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
-                   hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, HW, C, Cr,
-                   ws2.data_ptr(), ws2.numel(), int(g.dtype == torch.float16), L.stream())
-        else:
-            L.call("hyres_se_bwd", x.ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
-                   hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, HW, C, Cr,
-                   ws2.data_ptr(), ws2.numel(), L.stream())
+        L.call("hyres_se_bwd", x.ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
+               hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, HW, C, Cr,
+               ws2.data_ptr(), ws2.numel(), L.dt_mask(x, g), L.stream())
         if acc:
             accumulate(gx, tgt)
 
@@ -132,9 +116,8 @@ def spatial_attention_map(x: Node, w: torch.Tensor, keep: bool = False):
     pooled2 = _empty((B, H, W, 2), dev)
     argmax = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     attn = _empty((B, H, W), dev)
-    fn = "hyres_spatial_attn_fwd_f16" if x.half else "hyres_spatial_attn_fwd"
-    L.call(fn, x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(), attn.data_ptr(), None, B, H, W, C,
-           L.stream())
+    L.call("hyres_spatial_attn_fwd", x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(), attn.data_ptr(), None,
+           B, H, W, C, int(x.half), L.stream())
     return (attn, pooled2, argmax) if keep else attn
 
 
@@ -152,7 +135,7 @@ def sa_fold_fusion(tape: Optional[Tape], multi: Node, w_sa: torch.Tensor, weight
     (refine's 192-channel concat read and written three more times per step).
 
     Round 6, AMP training (``sa_fold_amp_ok``): fp16 ``multi``, output, pre-activation and gradients, fp16 operands on
-    the f16 MFMA; backward hyres_sa_fold_bwd_f16, the input-gradient on conv1x1_stream_hf_kernel's SA_BWD build."""
+    the f16 MFMA; backward hyres_sa_fold_bwd with the fp16 mask, the input-gradient on conv1x1_stream_hf_kernel's SA_BWD build."""
     assert multi.contiguous and (not multi.half or sa_fold_amp_ok(tape, multi, weight.shape[0]))
     Co, Ci_w, KH, KW = weight.shape
     assert KH == 1 and KW == 1 and Ci_w == multi.C and slope.numel() == 1
@@ -189,14 +172,9 @@ def sa_fold_fusion(tape: Optional[Tape], multi: Node, w_sa: torch.Tensor, weight
         ws = _ws(L.load().hyres_sa_fold_workspace_bytes(P, Co), dev, slot=1)
         dbias = param_grad(bias) if bias.requires_grad else _empty((Co,), dev)
         dslope = param_grad(slope) if slope.requires_grad else _empty((1,), dev)
-        if pre.dtype == torch.float16:
-            L.call("hyres_sa_fold_bwd_f16", pre.data_ptr(), Co, gy.data_ptr(), y.grad_ld(), attn.data_ptr(),
-                   bias.data_ptr(), slope.data_ptr(), gs.data_ptr(), glogit.data_ptr(), dbias.data_ptr(),
-                   dslope.data_ptr(), P, Co, ws.data_ptr(), ws.numel(), int(gy.dtype == torch.float16), L.stream())
-        else:
-            L.call("hyres_sa_fold_bwd", pre.data_ptr(), Co, gy.data_ptr(), y.grad_ld(), attn.data_ptr(),
-                   bias.data_ptr(), slope.data_ptr(), gs.data_ptr(), glogit.data_ptr(), dbias.data_ptr(),
-                   dslope.data_ptr(), P, Co, ws.data_ptr(), ws.numel(), L.stream())
+        L.call("hyres_sa_fold_bwd", pre.data_ptr(), Co, gy.data_ptr(), y.grad_ld(), attn.data_ptr(), bias.data_ptr(),
+               slope.data_ptr(), gs.data_ptr(), glogit.data_ptr(), dbias.data_ptr(), dslope.data_ptr(), P, Co,
+               ws.data_ptr(), ws.numel(), L.dt_mask(pre, gy), L.stream())
         gp2 = _empty((B, H, W, 2), dev)
         gw_sa = param_grad(w_sa) if w_sa.requires_grad else _empty(w_sa.shape, dev)
         ws2 = _ws(L.load().hyres_spatial_attn_workspace_bytes(B, H, W), dev, slot=1)
@@ -208,7 +186,7 @@ def sa_fold_fusion(tape: Optional[Tape], multi: Node, w_sa: torch.Tensor, weight
             d.sm = Ci_w
             d.accumulate = 1
             d.f16_operands = f16 * O.AMP_WGRAD_F16
-            d.io_f16 = (1 if gs.dtype == torch.float16 else 0) | (2 if multi.half else 0)
+            d.io_f16 = L.dt_mask(gs, multi, 1, 2)
             O._wgrad(d, gs.data_ptr(), multi.ptr(), param_grad(weight), dev, None, keep=(gs, multi.v), side=True)
         if multi.rg:
             ed = L.Epilogue()
@@ -283,9 +261,8 @@ def spatial_attention_mul(tape: Optional[Tape], x: Node, w: torch.Tensor) -> Nod
     argmax = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     attn = _empty((B, H, W), dev)
     y = Node.new(B, H, W, C, dev, dtype=x.v.dtype)
-    fn = "hyres_spatial_attn_fwd_f16" if x.half else "hyres_spatial_attn_fwd"
-    L.call(fn, x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(), attn.data_ptr(), y.ptr(), B, H, W, C,
-           L.stream())
+    L.call("hyres_spatial_attn_fwd", x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(), attn.data_ptr(),
+           y.ptr(), B, H, W, C, int(x.half), L.stream())
     if tape is None:
         return y
 
@@ -300,14 +277,9 @@ def spatial_attention_mul(tape: Optional[Tape], x: Node, w: torch.Tensor) -> Nod
         gw = param_grad(w) if w.requires_grad else _empty(w.shape, dev)
         wsb = L.load().hyres_spatial_attn_workspace_bytes(B, H, W)
         ws = _ws(wsb, dev, slot=1)
-        if x.half:
-            L.call("hyres_spatial_attn_bwd_f16", x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(),
-                   attn.data_ptr(), g.data_ptr(), gx.data_ptr(), gw.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(),
-                   int(g.dtype == torch.float16), L.stream())
-        else:
-            L.call("hyres_spatial_attn_bwd", x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(),
-                   attn.data_ptr(), g.data_ptr(), gx.data_ptr(), gw.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(),
-                   L.stream())
+        L.call("hyres_spatial_attn_bwd", x.ptr(), w.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(), attn.data_ptr(),
+               g.data_ptr(), gx.data_ptr(), gw.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(), L.dt_mask(x, g),
+               L.stream())
         if acc:
             accumulate(gx, tgt)
 

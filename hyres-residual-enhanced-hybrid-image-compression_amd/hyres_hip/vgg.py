@@ -118,7 +118,7 @@ class VGGLoss(nn.Module):
                 if acc:
                     t = _empty(tuple(x.v.shape), x.device)
                     L.call("hyres_relu_bwd", y.ptr(), g.data_ptr(), t.data_ptr(), x.P * x.C, L.stream())
-                    L.call("hyres_accumulate", t.data_ptr(), tgt.data_ptr(), t.numel(), L.stream())
+                    L.call("hyres_accumulate", t.data_ptr(), tgt.data_ptr(), t.numel(), 0, L.stream())
                 else:
                     L.call("hyres_relu_bwd", y.ptr(), g.data_ptr(), tgt.data_ptr(), x.P * x.C, L.stream())
             tape.push(bwd)

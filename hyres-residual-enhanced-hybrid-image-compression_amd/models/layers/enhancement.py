@@ -52,7 +52,7 @@ class SpatialAttention(HipModule):
         attn = Node.new(B, H, W, 1, x.device)
         y = O._empty((B, H, W, C), x.device)
         L.call("hyres_spatial_attn_fwd", x.ptr(), self.conv.weight.data_ptr(), pooled2.data_ptr(), argmax.data_ptr(),
-               attn.ptr(), y.data_ptr(), B, H, W, C, L.stream())
+               attn.ptr(), y.data_ptr(), B, H, W, C, 0, L.stream())
         return attn
 
 

@@ -124,7 +124,7 @@ int hyres_conv_weight_prep_batch(const void* descs, int n, long long total, hyre
                                 * prelu_bwd (its PReLU output is multi[..., 0:64], enhancement.py:113-115) */
 #define HYRES_PRELU_PARTIALS 2048
 
-#define HYRES_IO_X16 1   /* hyres_epilogue.io_f16 bits */
+#define HYRES_IO_X16 1   /* hyres_epilogue.io_f16 bits; X16 / Y16 also hyres_add2d's io */
 #define HYRES_IO_Y16 2
 #define HYRES_IO_AUX16 4
 typedef struct hyres_epilogue {
@@ -301,13 +301,30 @@ int hyres_ru_fused_f16(const void* x, void* y, int B, int H, int W, int N, const
 /* t1, t2: NULL (inference), or [B][H][W][N/2] fp16 outputs receiving the two intermediates (AMP training: the
  * backward of the three convs reads them). */
 
-/* column sums over pixels: dst[c] (+)= sum_p x[p*ld + c]  (bias gradients) */
-int hyres_colsum(const float* x, int P, int C, int ld, float* dst, int accumulate, void* workspace,
-                 long long ws_bytes, hyres_stream_t s);
+/* ------------------------------------------------------------------------------------------ */
+/* operand dtypes of the element-wise and MultiScaleRefine entry points                       */
+/* ------------------------------------------------------------------------------------------ */
+/* The activation / gradient operands of these entry points are ``void*``: fp32, or fp16 in HBM (autocast inference
+ * and AMP training) with fp32 arithmetic either way. Their last argument before the stream says which:
+ *  - ``int dt`` (entry points with both operand classes), a mask of
+ *      HYRES_DT_ACT16:  the SAVED activations the forward wrote (y, x, pre, a / b, the GDN norm) are fp16;
+ *      HYRES_DT_GRAD16: the gradients in and out (g, gy, gx, ga / gb, dn, gs) are fp16 — autocast's own semantics
+ *                       inside the f16 region (the gradient of an fp16 tensor is fp16, src/utils/engine.py:32,50-53).
+ *    Kernels exist for 0, ACT16 and ACT16 | GRAD16; GRAD16 alone (fp16 gradients of fp32 activations) and any other
+ *    value are HYRES_E_ARG — except hyres_bilinear_bwd_prelu, which has all four.
+ *  - ``int f16`` (entry points with one operand class): 0 = fp32, 1 = fp16; anything else is HYRES_E_ARG.
+ *  - hyres_add2d's two-sided ``int io``: HYRES_IO_X16 | HYRES_IO_Y16.
+ * The value is checked first, before any pointer and before any launch. Parameters, weight gradients and the saved
+ * fp32 side tensors (pooled, attn, ...) stay ``float*``. Vector paths need 4-element alignment of the operand: 16 B
+ * as fp32, 8 B as fp16; where an fp32 entry falls back to a scalar kernel on a ragged / misaligned operand and the
+ * fp16 form has no scalar kernel, that is said at the entry point. */
+#define HYRES_DT_ACT16 1
+#define HYRES_DT_GRAD16 2
+
+/* column sums over pixels: dst[c] (+)= sum_p x[p*ld + c]  (bias gradients); x fp32 / fp16 (f16), fp32 sums */
+int hyres_colsum(const void* x, int P, int C, int ld, float* dst, int accumulate, void* workspace,
+                 long long ws_bytes, int f16, hyres_stream_t s);
 long long hyres_colsum_workspace_bytes(int P, int C);
-/* the same over a fp16 x (AMP fp16 gradients), fp32 sums */
-int hyres_colsum_f16(const void* x, int P, int C, int ld, float* dst, int accumulate, void* workspace,
-                     long long ws_bytes, hyres_stream_t s);
 
 /* ------------------------------------------------------------------------------------------ */
 /* layout / elementwise                                                                       */
@@ -322,50 +339,31 @@ int hyres_add_clamp01_bwd(const float* pre, const float* g, float* gx, int accum
                           hyres_stream_t s);
 /* g_out = g * (y > 0)   (ReLU backward), optional accumulate into dst */
 int hyres_relu_bwd(const float* y, const float* g, float* gx, long long n, hyres_stream_t s);
-/* strided variant over NHWC slices */
-int hyres_relu_bwd_2d(const float* y, int ldy_, const float* g, int ldg, float* gx, int ldgx, long long P,
-                      int C, hyres_stream_t s);
+/* strided variant over NHWC slices (dtypes: "operand dtypes" above; y is the saved activation) */
+int hyres_relu_bwd_2d(const void* y, int ldy_, const void* g, int ldg, void* gx, int ldgx, long long P,
+                      int C, int dt, hyres_stream_t s);
 /* PReLU backward from the saved pre-activation x: gx = g*(x>0 ? 1 : a); dslope += sum(g*x*(x<=0))
  * (enhancement.py nn.PReLU). ws: hyres_reduce_workspace_bytes(P*C). */
-int hyres_prelu_bwd(const float* x, int ldx, const float* g, int ldg, float* gx, int ldgx, long long P,
-                    int C, const float* slope, float* dslope, void* ws, long long ws_bytes,
+int hyres_prelu_bwd(const void* x, int ldx, const void* g, int ldg, void* gx, int ldgx, long long P,
+                    int C, const float* slope, float* dslope, void* ws, long long ws_bytes, int dt,
                     hyres_stream_t s);
-/* AttentionBlock gate (models/layers/attention.py:44-47): out = a*sigmoid(b) + x */
-int hyres_attn_gate_fwd(const float* a, const float* b, const float* x, float* out, long long n,
+/* AttentionBlock gate (models/layers/attention.py:44-47): out = a*sigmoid(b) + x. f16 (autocast inference: a, b, x,
+ * out fp16) needs n % 4 == 0 and has no scalar kernel; fp32 falls back to one on a ragged n or a misaligned operand. */
+int hyres_attn_gate_fwd(const void* a, const void* b, const void* x, void* out, long long n, int f16,
                         hyres_stream_t s);
-/* fp16 activations (autocast inference): a, b, x, out fp16 in HBM, n % 4 == 0, 8B-aligned. */
-int hyres_attn_gate_fwd_f16(const void* a, const void* b, const void* x, void* out, long long n, hyres_stream_t s);
-int hyres_attn_gate_bwd(const float* a, const float* b, const float* g, float* ga, float* gb,
-                        long long n, hyres_stream_t s);
+/* a, b are the saved activations, g / ga / gb the gradients; a ragged n or a misaligned operand runs the scalar kernel */
+int hyres_attn_gate_bwd(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int dt,
+                        hyres_stream_t s);
 /* The same with the ReLU backward of a folded in (a = the last ResidualUnit's ReLU output, models/layers/attention.py:
- * 11-30, 44-47): ga = (a > 0) ? g * sigmoid(b) : 0. n % 4 == 0, every operand 16B-aligned (round 6). */
-int hyres_attn_gate_bwd_relu(const float* a, const float* b, const float* g, float* ga, float* gb, long long n,
+ * 11-30, 44-47): ga = (a > 0) ? g * sigmoid(b) : 0. n % 4 == 0 and every operand aligned are REQUIRED (round 6). */
+int hyres_attn_gate_bwd_relu(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int dt,
                              hyres_stream_t s);
-/* Backward passes with fp16 SAVED activations (AMP training: the forward wrote y / pre / a, b / x / norm as
- * fp16; fp32 arithmetic; 8B-aligned fp16 operands): same semantics as the fp32 entry points of the same name
- * without the suffix. g16 = 1: the gradients in and out (g, gx / ga, gb) are fp16 as well — autocast's own
- * semantics inside the f16 region (the gradient of an fp16 tensor is fp16, src/utils/engine.py:32,50-53);
- * g16 = 0: fp32 gradients. */
-int hyres_relu_bwd_2d_f16(const void* y, int ldy_, const void* g, int ldg, void* gx, int ldgx, long long P,
-                          int C, int g16, hyres_stream_t s);
-int hyres_prelu_bwd_f16(const void* x, int ldx, const void* g, int ldg, void* gx, int ldgx, long long P,
-                        int C, const float* slope, float* dslope, void* ws, long long ws_bytes, int g16,
-                        hyres_stream_t s);
-int hyres_attn_gate_bwd_f16(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int g16,
-                            hyres_stream_t s);
-/* ... and with the last ResidualUnit's ReLU backward folded in, as hyres_attn_gate_bwd_relu (round 6); n % 4 == 0,
- * fp16 operands 8B-aligned, fp32 ones 16B-aligned */
-int hyres_attn_gate_bwd_relu_f16(const void* a, const void* b, const void* g, void* ga, void* gb, long long n, int g16,
-                                 hyres_stream_t s);
-/* y (+)= x  (gradient fan-in); _f16: both fp16 */
-int hyres_accumulate(const float* x, float* y, long long n, hyres_stream_t s);
-int hyres_accumulate_f16(const void* x, void* y, long long n, hyres_stream_t s);
-/* y[p*ldy + c] (+)= x[p*ldx + c]  over P pixels x C channels (strided gradient fan-in / copy) */
-int hyres_add2d(const float* x, int ldx, float* y, int ldy, long long P, int C, int accumulate,
+/* y (+)= x  (gradient fan-in); f16: both fp16 */
+int hyres_accumulate(const void* x, void* y, long long n, int f16, hyres_stream_t s);
+/* y[p*ldy + c] (+)= x[p*ldx + c]  over P pixels x C channels (strided gradient fan-in / copy), fp32 add;
+ * io: HYRES_IO_X16 = x fp16, HYRES_IO_Y16 = y fp16, 0 = both fp32 */
+int hyres_add2d(const void* x, int ldx, void* y, int ldy, long long P, int C, int accumulate, int io,
                 hyres_stream_t s);
-/* the same with fp16 storage: io bit 0 = x fp16, bit 1 = y fp16 (fp32 add) */
-int hyres_add2d_f16(const void* x, int ldx, void* y, int ldy, long long P, int C, int accumulate, int io,
-                    hyres_stream_t s);
 /* y = a * b elementwise (in-place allowed: CheckboardMaskedConv2d's weight.data *= mask) */
 int hyres_mul(const float* a, const float* b, float* y, long long n, hyres_stream_t s);
 /* stream-ordered memset 0 (hipMemsetAsync) */
@@ -381,12 +379,9 @@ int hyres_gdn_reparam_fwd(const float* beta, const float* gamma, float* beta_p, 
 int hyres_gdn_reparam_bwd(const float* beta, const float* gamma, const float* dbeta_p,
                           const float* dgamma_p, float* dbeta, float* dgamma, int C, int accumulate,
                           hyres_stream_t s);
-/* GDN backward helper: dn = g * y / n * (-0.5 GDN | +0.5 IGDN) */
-int hyres_gdn_dnorm(const float* g, const float* y, const float* n, float* dn, long long P, int C,
-                    int inverse, hyres_stream_t s);
-/* the same with fp16 y and n (AMP training); g16: g and dn fp16 too */
-int hyres_gdn_dnorm_f16(const void* g, const void* y, const void* n, void* dn, long long P, int C,
-                        int inverse, int g16, hyres_stream_t s);
+/* GDN backward helper: dn = g * y / n * (-0.5 GDN | +0.5 IGDN); y, n the saved activations, g, dn the gradients */
+int hyres_gdn_dnorm(const void* g, const void* y, const void* n, void* dn, long long P, int C,
+                    int inverse, int dt, hyres_stream_t s);
 
 /* ------------------------------------------------------------------------------------------ */
 /* quantisation, checkerboard context, entropy models                                         */
@@ -448,91 +443,69 @@ int hyres_eb_aux_loss(const float* packed, const float* quantiles, const float* 
 /* ------------------------------------------------------------------------------------------ */
 /* MultiScaleRefine pieces (models/layers/enhancement.py)                                     */
 /* ------------------------------------------------------------------------------------------ */
-/* bilinear, align_corners=False, torch source-index rule (scale = in/out, or 1/scale_factor). */
-int hyres_bilinear_fwd(const float* x, int ldx, float* y, int ldy, int B, int Hi, int Wi, int Ho, int Wo,
-                       int C, float scale_h, float scale_w, int accumulate, hyres_stream_t s);
-int hyres_bilinear_bwd(const float* gy, int ldgy, float* gx, int ldgx, int B, int Hi, int Wi, int Ho,
-                       int Wo, int C, float scale_h, float scale_w, int accumulate, hyres_stream_t s);
-/* SEBlock (enhancement.py:25-40): s = sigmoid(W2 relu(W1 mean_hw(x))); y = x*s */
-int hyres_se_fwd(const float* x, const float* w1, const float* w2, float* y, float* pooled,
-                 float* hidden, float* sgate, int B, int HW, int C, int Cr, void* ws, long long ws_bytes,
+/* bilinear, align_corners=False, torch source-index rule (scale = in/out, or 1/scale_factor). f16 (x / y, or the
+ * gradients gy / gx, fp16): the forward then needs C % 4 == 0, ld % 4 == 0, 8B-aligned x / y and takes no accumulate
+ * (HYRES_E_ARG); the fp32 forward and both backward forms have scalar kernels. */
+int hyres_bilinear_fwd(const void* x, int ldx, void* y, int ldy, int B, int Hi, int Wi, int Ho, int Wo,
+                       int C, float scale_h, float scale_w, int accumulate, int f16, hyres_stream_t s);
+int hyres_bilinear_bwd(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho,
+                       int Wo, int C, float scale_h, float scale_w, int accumulate, int f16, hyres_stream_t s);
+/* SEBlock (enhancement.py:25-40): s = sigmoid(W2 relu(W1 mean_hw(x))); y = x*s. pooled / hidden / sgate fp32.
+ * f16 (x, y fp16) needs C % 4 == 0, 256 % (C/4) == 0 and 8B-aligned x / y (no scalar kernels). */
+int hyres_se_fwd(const void* x, const float* w1, const float* w2, void* y, float* pooled,
+                 float* hidden, float* sgate, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, int f16,
                  hyres_stream_t s);
-int hyres_se_bwd(const float* x, const float* gy, const float* w1, const float* w2,
-                 const float* pooled, const float* hidden, const float* sgate, float* gx, float* gw1,
-                 float* gw2, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, hyres_stream_t s);
+/* x the saved activation, gy / gx the gradients; weight gradients fp32 */
+int hyres_se_bwd(const void* x, const void* gy, const float* w1, const float* w2,
+                 const float* pooled, const float* hidden, const float* sgate, void* gx, float* gw1,
+                 float* gw2, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, int dt, hyres_stream_t s);
 /* hyres_se_bwd with the backward of the PReLU that produced x folded in (round 6; MultiScaleRefine's
  * SE(PReLU(conv_in(x))), enhancement.py:107-110): gx = PReLU'(pre) * dL/dx, the slope gradient
- * sum_{pre <= 0} pre * dL/dx ADDED to dslope[0] (block partials in the workspace, fixed-order sum). fp32; the
- * workspace is hyres_se_workspace_bytes + B*C*4 + 2048*4 bytes. Replaces prelu_bwd after the SE backward. */
-int hyres_se_bwd_prelu(const float* x, const float* gy, const float* w1, const float* w2, const float* pooled,
-                       const float* hidden, const float* sgate, float* gx, float* gw1, float* gw2, int B, int HW, int C,
-                       int Cr, const float* pre, const float* slope, float* dslope, void* ws, long long ws_bytes,
+ * sum_{pre <= 0} pre * dL/dx ADDED to dslope[0] (block partials in the workspace, fixed-order sum). pre has x's
+ * dtype; with fp16 gradients the gradient is rounded to fp16 before the PReLU, as the unfused chain stores it.
+ * C % 4 == 0 and aligned gy / gx / pre are required; the workspace is hyres_se_workspace_bytes + B*C*4 + 2048*4
+ * bytes. Replaces prelu_bwd after the SE backward. */
+int hyres_se_bwd_prelu(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
+                       const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW, int C,
+                       int Cr, const void* pre, const float* slope, float* dslope, void* ws, long long ws_bytes, int dt,
                        hyres_stream_t s);
 long long hyres_se_workspace_bytes(int B, int HW, int C);
 /* SpatialAttention (enhancement.py:7-21) fused: a = sigmoid(conv7x7([mean_c, max_c])); y = x * a.
- * pooled2 [P][2] and argmax [P] (first maximal channel, torch.max semantics) are saved for backward.
- * C % 4 == 0, 16B-aligned x/y/gy/gx. */
-int hyres_spatial_attn_fwd(const float* x, const float* w, float* pooled2, int* argmax, float* attn,
-                           float* y, int B, int H, int W, int C, hyres_stream_t s);
-int hyres_spatial_attn_bwd(const float* x, const float* w, const float* pooled2, const int* argmax,
-                           const float* attn, const float* gy, float* gx, float* gw, int B, int H, int W,
-                           int C, void* ws, long long ws_bytes, hyres_stream_t s);
+ * pooled2 [P][2] and argmax [P] (first maximal channel, torch.max semantics) are saved for backward, fp32 / int
+ * like attn. C % 4 == 0, aligned x/y/gy/gx. y == NULL: the attention map only. */
+int hyres_spatial_attn_fwd(const void* x, const float* w, float* pooled2, int* argmax, float* attn,
+                           void* y, int B, int H, int W, int C, int f16, hyres_stream_t s);
+int hyres_spatial_attn_bwd(const void* x, const float* w, const float* pooled2, const int* argmax,
+                           const float* attn, const void* gy, void* gx, float* gw, int B, int H, int W,
+                           int C, void* ws, long long ws_bytes, int dt, hyres_stream_t s);
 long long hyres_spatial_attn_workspace_bytes(int B, int H, int W);
 /* Training with SpatialAttention's multiply folded into MultiScaleRefine's fusion 1x1 (HYRES_EPI_ROWSCALE forward,
  * enhancement.py:105-109): h = PReLU(attn[p] * (W multi)[p] + b), ``pre`` its pre-activation [P][C] (C = fusion
  * width, ldpre), gy = dL/dh [P][ldg]. Writes gs = attn[p] * gp (gp = PReLU-backward of gy: the fusion 1x1's weight-
  * and input-gradient operand), glogit[p] = (1 - attn[p]) * sum_o gp[p,o] * (pre[p,o] - b[o]) (= the gradient at the
  * attention logit: attn * z = pre - b, no division), and ADDS dbias += sum_p gp, dslope += sum_{pre <= 0} gy * pre
- * (deterministic per-block partials). C % 4 == 0, C <= 64, 16B-aligned rows; ws >= hyres_sa_fold_workspace_bytes(P, C). */
+ * (deterministic per-block partials). ``pre`` is the saved activation, gy / gs the gradients; attn, bias, glogit, dbias,
+ * dslope fp32. C % 4 == 0 (fp16 pre: C, ldpre, ldg % 8 == 0), C <= 64, 16B-aligned rows;
+ * ws >= hyres_sa_fold_workspace_bytes(P, C). */
 long long hyres_sa_fold_workspace_bytes(long long P, int C);
-int hyres_sa_fold_bwd(const float* pre, int ldpre, const float* gy, int ldg, const float* attn, const float* bias,
-                      const float* slope, float* gs, float* glogit, float* dbias, float* dslope, long long P, int C,
-                      void* ws, long long ws_bytes, hyres_stream_t s);
-/* ... under AMP training (round 6): ``pre`` fp16 (fp16 activations); g16 = 1: gy and gs fp16 as well (fp16
- * gradients), 0: fp32. fp32 arithmetic; attn, bias, glogit, dbias, dslope fp32. C % 8 == 0, C <= 64, rows 16B-aligned. */
-int hyres_sa_fold_bwd_f16(const void* pre, int ldpre, const void* gy, int ldg, const float* attn, const float* bias,
-                          const float* slope, void* gs, float* glogit, float* dbias, float* dslope, long long P, int C,
-                          void* ws, long long ws_bytes, int g16, hyres_stream_t s);
+int hyres_sa_fold_bwd(const void* pre, int ldpre, const void* gy, int ldg, const float* attn, const float* bias,
+                      const float* slope, void* gs, float* glogit, float* dbias, float* dslope, long long P, int C,
+                      void* ws, long long ws_bytes, int dt, hyres_stream_t s);
 /* SpatialAttention's map backward from the logit gradient: gw += d conv7x7 weight, gpooled2 = [P][2] gradients of
  * the channel mean (already divided by C, as HYRES_EPI_SA_BWD reads it) and the channel max. ws as
  * hyres_spatial_attn_workspace_bytes(B, H, W). */
 int hyres_spatial_attn_bwd_map(const float* glogit, const float* pooled2, const float* w, float* gpooled2, float* gw,
                                int B, int H, int W, int C, void* ws, long long ws_bytes, hyres_stream_t s);
-/* fp16-activation forwards (x and y fp16 in HBM, fp32 arithmetic; autocast inference, BASELINE
- * configs[4] "fp16 activations"): same semantics as the fp32 forwards above (bilinear without
- * accumulate; C % 4 == 0, ld % 4 == 0, 8B-aligned x/y). pooled / hidden / sgate / pooled2 / attn fp32. */
-int hyres_bilinear_fwd_f16(const void* x, int ldx, void* y, int ldy, int B, int Hi, int Wi, int Ho, int Wo,
-                           int C, float scale_h, float scale_w, hyres_stream_t s);
-int hyres_se_fwd_f16(const void* x, const float* w1, const float* w2, void* y, float* pooled, float* hidden,
-                     float* sgate, int B, int HW, int C, int Cr, void* ws, long long ws_bytes, hyres_stream_t s);
-int hyres_spatial_attn_fwd_f16(const void* x, const float* w, float* pooled2, int* argmax, float* attn,
-                               void* y, int B, int H, int W, int C, hyres_stream_t s);
-/* their backward passes with fp16 x (AMP training); g16 = 1: gy, gx fp16 too (autocast's fp16 activation
- * gradients), g16 = 0: gy, gx fp32. Weight gradients fp32. */
-int hyres_se_bwd_f16(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
-                     const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW,
-                     int C, int Cr, void* ws, long long ws_bytes, int g16, hyres_stream_t s);
-/* ... with the producing PReLU's backward folded in under AMP (round 6): pre fp16 (fp16 activations); g16 = 1: gy /
- * gx fp16 (the gradient rounded to fp16 before the PReLU, as the unfused chain stores it). As hyres_se_bwd_prelu. */
-int hyres_se_bwd_prelu_f16(const void* x, const void* gy, const float* w1, const float* w2, const float* pooled,
-                           const float* hidden, const float* sgate, void* gx, float* gw1, float* gw2, int B, int HW, int C,
-                           int Cr, const void* pre, const float* slope, float* dslope, void* ws, long long ws_bytes,
-                           int g16, hyres_stream_t s);
-int hyres_spatial_attn_bwd_f16(const void* x, const float* w, const float* pooled2, const int* argmax,
-                               const float* attn, const void* gy, void* gx, float* gw, int B, int H, int W,
-                               int C, void* ws, long long ws_bytes, int g16, hyres_stream_t s);
-/* bilinear backward over fp16 gy / gx (AMP fp16 gradients; fp32 sums; 8B-aligned when C % 4 == 0) */
-int hyres_bilinear_bwd_f16(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo,
-                           int C, float scale_h, float scale_w, int accumulate, hyres_stream_t s);
 /* Round 6: the up-sample's backward with the PReLU backward of the layer that produced its input folded in
  * (MultiScaleRefine scales 2 / 3: conv + PReLU, then the bilinear up-sample, enhancement.py:89-103): writes
  * gx = pre > 0 ? g : slope * g (g = the gather sum, rounded to fp16 first with fp16 gradients) — NOT accumulated, the
  * caller is the first writer — and ADDS dslope += sum_{pre <= 0} pre * g (deterministic block partials in ws).
- * io: bit 0 gy / gx fp16, bit 1 pre fp16. C % 4 == 0, aligned rows; ws >= hyres_bilinear_bwd_prelu_workspace_bytes. */
+ * dt: HYRES_DT_GRAD16 gy / gx fp16, HYRES_DT_ACT16 pre fp16 (all four masks). C % 4 == 0, aligned rows;
+ * ws >= hyres_bilinear_bwd_prelu_workspace_bytes. */
 long long hyres_bilinear_bwd_prelu_workspace_bytes(int B, int Hi, int Wi, int C);
 int hyres_bilinear_bwd_prelu(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
                              float scale_h, float scale_w, const void* pre, int ldpre, const float* slope, float* dslope,
-                             void* ws, long long ws_bytes, int io, hyres_stream_t s);
+                             void* ws, long long ws_bytes, int dt, hyres_stream_t s);
 
 /* ------------------------------------------------------------------------------------------ */
 /* losses and optimiser (src/losses/rd_loss.py:18-44, src/utils/engine.py:56-90)              */

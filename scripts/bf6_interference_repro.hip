@@ -232,7 +232,7 @@ int main(int argc, char** argv) {
         if (kind == 1) hipLaunchKernelGGL(victim<1>, grid, dim3(256), 0, s, dx, out);
         if (kind == 2) hipLaunchKernelGGL(victim<2>, grid, dim3(256), 0, s, dx, out);
         if (kind == 3) hipLaunchKernelGGL(victim<3>, grid, dim3(256), 0, s, dx, out);
-        if (kind == 4) CH(hyres_bilinear_fwd(dx, 64, out, 64, 2, 256, 256, 128, 128, 64, 2.0f, 2.0f, 0, s));
+        if (kind == 4) CH(hyres_bilinear_fwd(dx, 64, out, 64, 2, 256, 256, 128, 128, 64, 2.0f, 2.0f, 0, 0, s));
         if (kind == 5) {  // bf16x6 implicit GEMM while the hog's keys are restored by the next conv()
             CH(hyres_conv_tuning(HYRES_TUNE_F32_GEMM, 1, nullptr));
             CH(hyres_conv_tuning(HYRES_TUNE_WRES32, 0, nullptr));

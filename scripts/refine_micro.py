@@ -44,15 +44,15 @@ def main():
     st = L.stream()
     cases = [
         ("bilinear down x1/2", lambda: L.call("hyres_bilinear_fwd", feat.data_ptr(), C, h2.data_ptr(), C, B, H, H, H // 2,
-                                               H // 2, C, 2.0, 2.0, 0, st), 4 * B * C * (H * H + (H // 2) ** 2)),
+                                               H // 2, C, 2.0, 2.0, 0, 0, st), 4 * B * C * (H * H + (H // 2) ** 2)),
         ("bilinear up x2 -> concat", lambda: L.call("hyres_bilinear_fwd", h2.data_ptr(), C, multi[..., C:].data_ptr(),
-                                                    3 * C, B, H // 2, H // 2, H, H, C, 0.5, 0.5, 0, st),
+                                                    3 * C, B, H // 2, H // 2, H, H, C, 0.5, 0.5, 0, 0, st),
          4 * B * C * (H * H + (H // 2) ** 2)),
         ("bilinear down x1/4", lambda: L.call("hyres_bilinear_fwd", feat.data_ptr(), C, h4.data_ptr(), C, B, H, H, H // 4,
-                                               H // 4, C, 4.0, 4.0, 0, st), 4 * B * C * (H * H // 4 + (H // 4) ** 2)),
+                                               H // 4, C, 4.0, 4.0, 0, 0, st), 4 * B * C * (H * H // 4 + (H // 4) ** 2)),
         ("bilinear up x4 -> concat", lambda: L.call("hyres_bilinear_fwd", h4.data_ptr(), C,
                                                     multi[..., 2 * C:].data_ptr(), 3 * C, B, H // 4, H // 4, H, H, C,
-                                                    0.25, 0.25, 0, st), 4 * B * C * (H * H + (H // 4) ** 2)),
+                                                    0.25, 0.25, 0, 0, st), 4 * B * C * (H * H + (H // 4) ** 2)),
     ]
     P = B * H * H
     w = torch.randn(1, 2, 7, 7, device=D)
@@ -62,7 +62,7 @@ def main():
     y = torch.empty_like(multi)
     cases.append(("spatial attention fwd (C=192)", lambda: L.call(
         "hyres_spatial_attn_fwd", multi.data_ptr(), w.data_ptr(), pooled2.data_ptr(), amax.data_ptr(), attn.data_ptr(),
-        y.data_ptr(), B, H, H, 3 * C, st), 4 * P * 3 * C * 3))
+        y.data_ptr(), B, H, H, 3 * C, 0, st), 4 * P * 3 * C * 3))
     for name, fn, byts in cases:
         us = timeit(fn, a.iters)
         print(f"{name:32s} B{B} {H}^2: {us:8.1f} us, {byts / us / 1e3:6.0f} GB/s (algorithmic {byts / 1e6:.0f} MB)")

@@ -38,6 +38,20 @@ def _h(t):
 
 
 # ------------------------------------------------------------------------------------------ elementwise
+def _check_rounded(got16, want32, what):
+    # bit for bit, except that the compiler may fuse a kernel's last fp32 multiply with the fp16 store
+    # (v_fma_mixlo_f16: ONE rounding of the exact product, where fp32-then-fp16 rounds twice) — that differs by
+    # one fp16 ulp at double-rounding ties only: a handful of elements, never more than 1 ulp
+    want = want32.half()
+    if not torch.equal(got16, want):
+        bad = (got16 != want).nonzero()
+        m = got16 != want  # (+0 / -0 compare equal)
+        ulps = (got16[m].view(torch.int16).int() - want[m].view(torch.int16).int()).abs().max().item()
+        print(what, "mismatches", bad.shape[0], "max ulps", ulps, got16[tuple(bad[0])].item(),
+              want[tuple(bad[0])].item())
+        assert ulps <= 1 and bad.shape[0] <= max(4, got16.numel() // 4096), what
+
+
 def test_f16_saved_activation_backward_entry_points_bitwise():
     """relu / PReLU / attention gate / GDN dnorm / SE / spatial-attention backward with fp16 saved operands
     equal the fp32 entry points on the same (fp16-representable) values, bit for bit — except where a sum of
@@ -52,13 +66,14 @@ checked to 1e-6."""
     y = _h(_rand((P, C), 1)).to(D)
     g = _rand((P, C), 2).to(D)
     s = L.stream()
+    A16 = L.DT_ACT16
 
     def pair(name, args16, args32, outs, tol=None):
         res = []
-        for fn, args in ((name + "_f16", args16), (name, args32)):
+        for args in (args16, args32):  # the same entry point: the fp16-activation mask, then fp32
             for o in outs:
                 o.zero_()
-            L.call(fn, *args)
+            L.call(name, *args)
             res.append([o.clone() for o in outs])
         torch.cuda.synchronize()
         for k, (a, b) in enumerate(zip(*res)):
@@ -73,26 +88,26 @@ checked to 1e-6."""
 
     gx = torch.empty(P, C, device=D)
     yh = y.half()
-    pair("hyres_relu_bwd_2d", (yh.data_ptr(), C, g.data_ptr(), C, gx.data_ptr(), C, P, C, 0, s),
-         (y.data_ptr(), C, g.data_ptr(), C, gx.data_ptr(), C, P, C, s), [gx])
+    pair("hyres_relu_bwd_2d", (yh.data_ptr(), C, g.data_ptr(), C, gx.data_ptr(), C, P, C, A16, s),
+         (y.data_ptr(), C, g.data_ptr(), C, gx.data_ptr(), C, P, C, 0, s), [gx])
     slope = torch.tensor([0.25], device=D)
     dslope = torch.zeros(1, device=D)
     ws = torch.empty(int(L.load().hyres_reduce_workspace_bytes(P * C)), dtype=torch.uint8, device=D)
     pair("hyres_prelu_bwd", (yh.data_ptr(), C, g.data_ptr(), C, gx.data_ptr(), C, P, C, slope.data_ptr(),
-                             dslope.data_ptr(), ws.data_ptr(), ws.numel(), 0, s),
+                             dslope.data_ptr(), ws.data_ptr(), ws.numel(), A16, s),
          (y.data_ptr(), C, g.data_ptr(), C, gx.data_ptr(), C, P, C, slope.data_ptr(), dslope.data_ptr(),
-          ws.data_ptr(), ws.numel(), s), [gx, dslope], tol=[0, 1e-6])
+          ws.data_ptr(), ws.numel(), 0, s), [gx, dslope], tol=[0, 1e-6])
     b = _h(_rand((P, C), 3)).to(D)
     bh = b.half()
     ga, gb = torch.empty(P, C, device=D), torch.empty(P, C, device=D)
-    pair("hyres_attn_gate_bwd", (yh.data_ptr(), bh.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), P * C, 0, s),
-         (y.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), P * C, s), [ga, gb])
+    pair("hyres_attn_gate_bwd", (yh.data_ptr(), bh.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), P * C, A16, s),
+         (y.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), P * C, 0, s), [ga, gb])
     nrm = _h(_rand((P, C), 4).abs() + 0.5).to(D)
     nh = nrm.half()
     dn = torch.empty(P, C, device=D)
     for inv in (0, 1):
-        pair("hyres_gdn_dnorm", (g.data_ptr(), yh.data_ptr(), nh.data_ptr(), dn.data_ptr(), P, C, inv, 0, s),
-             (g.data_ptr(), y.data_ptr(), nrm.data_ptr(), dn.data_ptr(), P, C, inv, s), [dn])
+        pair("hyres_gdn_dnorm", (g.data_ptr(), yh.data_ptr(), nh.data_ptr(), dn.data_ptr(), P, C, inv, A16, s),
+             (g.data_ptr(), y.data_ptr(), nrm.data_ptr(), dn.data_ptr(), P, C, inv, 0, s), [dn])
     # SE / spatial attention: run the fp32 forward on the fp16-representable x for the saved state, then both
     # backward flavours
     Cr = 4
@@ -103,33 +118,33 @@ checked to 1e-6."""
     wsb = int(L.load().hyres_se_workspace_bytes(B, H * W, C)) + B * C * 4
     ws = torch.empty(wsb, dtype=torch.uint8, device=D)
     L.call("hyres_se_fwd", y.data_ptr(), w1.data_ptr(), w2.data_ptr(), yse.data_ptr(), pooled.data_ptr(),
-           hidden.data_ptr(), sgate.data_ptr(), B, H * W, C, Cr, ws.data_ptr(), ws.numel(), s)
+           hidden.data_ptr(), sgate.data_ptr(), B, H * W, C, Cr, ws.data_ptr(), ws.numel(), 0, s)
     gw1, gw2 = torch.zeros(Cr, C, device=D), torch.zeros(C, Cr, device=D)
     pair("hyres_se_bwd", (yh.data_ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
                           hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, H * W,
-                          C, Cr, ws.data_ptr(), ws.numel(), 0, s),
+                          C, Cr, ws.data_ptr(), ws.numel(), A16, s),
          (y.data_ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(), hidden.data_ptr(),
           sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, H * W, C, Cr, ws.data_ptr(),
-          ws.numel(), s), [gx, gw1, gw2])
+          ws.numel(), 0, s), [gx, gw1, gw2])
     wsa = _rand((1, 2, 7, 7), 7, 0.1).to(D)
     pooled2 = torch.empty(P, 2, device=D)
     amax = torch.empty(P, dtype=torch.int32, device=D)
     attn = torch.empty(P, device=D)
     ysa = torch.empty(P, C, device=D)
     L.call("hyres_spatial_attn_fwd", y.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(),
-           attn.data_ptr(), ysa.data_ptr(), B, H, W, C, s)
+           attn.data_ptr(), ysa.data_ptr(), B, H, W, C, 0, s)
     gw = torch.zeros(1, 2, 7, 7, device=D)
     wsb = int(L.load().hyres_spatial_attn_workspace_bytes(B, H, W))
     ws = torch.empty(wsb, dtype=torch.uint8, device=D)
     pair("hyres_spatial_attn_bwd", (yh.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(),
                                     attn.data_ptr(), g.data_ptr(), gx.data_ptr(), gw.data_ptr(), B, H, W, C,
-                                    ws.data_ptr(), ws.numel(), 0, s),
+                                    ws.data_ptr(), ws.numel(), A16, s),
          (y.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(), attn.data_ptr(), g.data_ptr(),
-          gx.data_ptr(), gw.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(), s), [gx, gw], tol=[1e-6, 1e-6])
+          gx.data_ptr(), gw.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(), 0, s), [gx, gw], tol=[1e-6, 1e-6])
 
 
 def test_f16_gradient_backward_entry_points_match_rounded_fp32():
-    """g16 = 1 (AMP fp16 activation gradients, autocast's own semantics): the same entry points with the incoming
+    """HYRES_DT_GRAD16 (AMP fp16 activation gradients, autocast's own semantics): the same entry points with the incoming
     gradient and the produced gradients fp16. Every kernel computes in fp32 from exactly converted operands and
     rounds its output once, so on fp16-representable inputs each fp16 gradient equals the fp32 entry point's
     result rounded to fp16, BIT FOR BIT (weight / slope gradients stay fp32: 1e-6 where FMA contraction may
@@ -143,70 +158,60 @@ def test_f16_gradient_backward_entry_points_match_rounded_fp32():
     yh = y.half()
     g = _h(_rand((P, C), 2)).to(D)
     gh = g.half()
+    AG16 = L.DT_ACT16 | L.DT_GRAD16  # fp16 saved activations and fp16 gradients
 
-    def check(got16, want32, what):
-        # bit for bit, except that the compiler may fuse a kernel's last fp32 multiply with the fp16 store
-        # (v_fma_mixlo_f16: ONE rounding of the exact product, where fp32-then-fp16 rounds twice) — that differs by
-        # one fp16 ulp at double-rounding ties only: a handful of elements, never more than 1 ulp
-        want = want32.half()
-        if not torch.equal(got16, want):
-            bad = (got16 != want).nonzero()
-            m = got16 != want  # (+0 / -0 compare equal)
-            ulps = (got16[m].view(torch.int16).int() - want[m].view(torch.int16).int()).abs().max().item()
-            print(what, "mismatches", bad.shape[0], "max ulps", ulps, got16[tuple(bad[0])].item(),
-                  want[tuple(bad[0])].item())
-            assert ulps <= 1 and bad.shape[0] <= max(4, got16.numel() // 4096), what
+    check = _check_rounded
 
     gx32, gx16 = torch.empty(P, C, device=D), torch.empty(P, C, device=D, dtype=torch.float16)
-    L.call("hyres_relu_bwd_2d", y.data_ptr(), C, g.data_ptr(), C, gx32.data_ptr(), C, P, C, s)
-    L.call("hyres_relu_bwd_2d_f16", yh.data_ptr(), C, gh.data_ptr(), C, gx16.data_ptr(), C, P, C, 1, s)
+    L.call("hyres_relu_bwd_2d", y.data_ptr(), C, g.data_ptr(), C, gx32.data_ptr(), C, P, C, 0, s)
+    L.call("hyres_relu_bwd_2d", yh.data_ptr(), C, gh.data_ptr(), C, gx16.data_ptr(), C, P, C, AG16, s)
     check(gx16, gx32, "relu")
     slope = torch.tensor([0.25], device=D)
     d32, d16 = torch.zeros(1, device=D), torch.zeros(1, device=D)
     ws = torch.empty(int(L.load().hyres_reduce_workspace_bytes(P * C)), dtype=torch.uint8, device=D)
     L.call("hyres_prelu_bwd", y.data_ptr(), C, g.data_ptr(), C, gx32.data_ptr(), C, P, C, slope.data_ptr(),
-           d32.data_ptr(), ws.data_ptr(), ws.numel(), s)
-    L.call("hyres_prelu_bwd_f16", yh.data_ptr(), C, gh.data_ptr(), C, gx16.data_ptr(), C, P, C, slope.data_ptr(),
-           d16.data_ptr(), ws.data_ptr(), ws.numel(), 1, s)
+           d32.data_ptr(), ws.data_ptr(), ws.numel(), 0, s)
+    L.call("hyres_prelu_bwd", yh.data_ptr(), C, gh.data_ptr(), C, gx16.data_ptr(), C, P, C, slope.data_ptr(),
+           d16.data_ptr(), ws.data_ptr(), ws.numel(), AG16, s)
     check(gx16, gx32, "prelu")
     assert rel_err(d16.cpu(), d32.cpu()) <= 1e-6
     b = _h(_rand((P, C), 3)).to(D)
     bh = b.half()
     ga32, gb32 = torch.empty(P, C, device=D), torch.empty(P, C, device=D)
     ga16, gb16 = torch.empty_like(gx16), torch.empty_like(gx16)
-    L.call("hyres_attn_gate_bwd", y.data_ptr(), b.data_ptr(), g.data_ptr(), ga32.data_ptr(), gb32.data_ptr(), P * C, s)
-    L.call("hyres_attn_gate_bwd_f16", yh.data_ptr(), bh.data_ptr(), gh.data_ptr(), ga16.data_ptr(), gb16.data_ptr(),
-           P * C, 1, s)
+    L.call("hyres_attn_gate_bwd", y.data_ptr(), b.data_ptr(), g.data_ptr(), ga32.data_ptr(), gb32.data_ptr(), P * C, 0, s)
+    L.call("hyres_attn_gate_bwd", yh.data_ptr(), bh.data_ptr(), gh.data_ptr(), ga16.data_ptr(), gb16.data_ptr(),
+           P * C, AG16, s)
     check(ga16, ga32, "gate a")
     check(gb16, gb32, "gate b")
     nrm = _h(_rand((P, C), 4).abs() + 0.5).to(D)
     nrm16 = nrm.half()  # held for the call (a temporary's block returns to the allocator before the kernel runs)
     for inv in (0, 1):
-        L.call("hyres_gdn_dnorm", g.data_ptr(), y.data_ptr(), nrm.data_ptr(), gx32.data_ptr(), P, C, inv, s)
-        L.call("hyres_gdn_dnorm_f16", gh.data_ptr(), yh.data_ptr(), nrm16.data_ptr(), gx16.data_ptr(), P, C, inv,
-               1, s)
+        L.call("hyres_gdn_dnorm", g.data_ptr(), y.data_ptr(), nrm.data_ptr(), gx32.data_ptr(), P, C, inv, 0, s)
+        L.call("hyres_gdn_dnorm", gh.data_ptr(), yh.data_ptr(), nrm16.data_ptr(), gx16.data_ptr(), P, C, inv,
+               AG16, s)
         check(gx16, gx32, f"gdn dnorm inv={inv}")
     # add2d with every storage combination, accumulate on and off
-    for io in (1, 2, 3):
+    for io in (L.IO_X16, L.IO_Y16, L.IO_X16 | L.IO_Y16):
         for acc in (0, 1):
             base = _h(_rand((P, C), 5)).to(D)
             dst32 = base.clone()
-            L.call("hyres_add2d", g.data_ptr(), C, dst32.data_ptr(), C, P, C, acc, s)
-            src = gh if io & 1 else g
-            dst = base.half() if io & 2 else base.clone()
-            L.call("hyres_add2d_f16", src.data_ptr(), C, dst.data_ptr(), C, P, C, acc, io, s)
-            if io & 2:
+            L.call("hyres_add2d", g.data_ptr(), C, dst32.data_ptr(), C, P, C, acc, 0, s)
+            src = gh if io & L.IO_X16 else g
+            dst = base.half() if io & L.IO_Y16 else base.clone()
+            L.call("hyres_add2d", src.data_ptr(), C, dst.data_ptr(), C, P, C, acc, io, s)
+            if io & L.IO_Y16:
                 check(dst, dst32, f"add2d io={io} acc={acc}")
             else:
                 assert torch.equal(dst, dst32), (io, acc)
     acc16 = y.half()
-    L.call("hyres_accumulate_f16", gh.data_ptr(), acc16.data_ptr(), P * C, s)
+    L.call("hyres_accumulate", gh.data_ptr(), acc16.data_ptr(), P * C, 1, s)
     check(acc16, y + g, "accumulate")
     # bias column sums over a fp16 gradient: the same sums as over its fp32 copy, bit for bit
     c32, c16 = torch.zeros(C, device=D), torch.zeros(C, device=D)
     wsc = torch.empty(int(L.load().hyres_colsum_workspace_bytes(P, C)), dtype=torch.uint8, device=D)
-    L.call("hyres_colsum", g.data_ptr(), P, C, C, c32.data_ptr(), 0, wsc.data_ptr(), wsc.numel(), s)
-    L.call("hyres_colsum_f16", gh.data_ptr(), P, C, C, c16.data_ptr(), 0, wsc.data_ptr(), wsc.numel(), s)
+    L.call("hyres_colsum", g.data_ptr(), P, C, C, c32.data_ptr(), 0, wsc.data_ptr(), wsc.numel(), 0, s)
+    L.call("hyres_colsum", gh.data_ptr(), P, C, C, c16.data_ptr(), 0, wsc.data_ptr(), wsc.numel(), 1, s)
     torch.cuda.synchronize()
     assert torch.equal(c16, c32)
     # bilinear backward (general gather and the exact x1/2 down-sampling kernel), accumulate on
@@ -214,8 +219,8 @@ def test_f16_gradient_backward_entry_points_match_rounded_fp32():
         gy = _h(_rand((B * Ho * Wo, C), 6)).to(D)
         base = _h(_rand((P, C), 7)).to(D)
         o32, o16, gy16 = base.clone(), base.half(), gy.half()
-        L.call("hyres_bilinear_bwd", gy.data_ptr(), C, o32.data_ptr(), C, B, Hi, Wi, Ho, Wo, C, sc, sc, 1, s)
-        L.call("hyres_bilinear_bwd_f16", gy16.data_ptr(), C, o16.data_ptr(), C, B, Hi, Wi, Ho, Wo, C, sc, sc, 1, s)
+        L.call("hyres_bilinear_bwd", gy.data_ptr(), C, o32.data_ptr(), C, B, Hi, Wi, Ho, Wo, C, sc, sc, 1, 0, s)
+        L.call("hyres_bilinear_bwd", gy16.data_ptr(), C, o16.data_ptr(), C, B, Hi, Wi, Ho, Wo, C, sc, sc, 1, 1, s)
         check(o16, o32, f"bilinear bwd {Ho}x{Wo}")
     # SE / spatial attention backward with fp16 gy / gx
     Cr = 4
@@ -226,15 +231,15 @@ def test_f16_gradient_backward_entry_points_match_rounded_fp32():
     wsb = int(L.load().hyres_se_workspace_bytes(B, H * W, C)) + B * C * 4
     ws = torch.empty(wsb, dtype=torch.uint8, device=D)
     L.call("hyres_se_fwd", y.data_ptr(), w1.data_ptr(), w2.data_ptr(), yse.data_ptr(), pooled.data_ptr(),
-           hidden.data_ptr(), sgate.data_ptr(), B, H * W, C, Cr, ws.data_ptr(), ws.numel(), s)
+           hidden.data_ptr(), sgate.data_ptr(), B, H * W, C, Cr, ws.data_ptr(), ws.numel(), 0, s)
     gws = [torch.zeros(Cr, C, device=D), torch.zeros(C, Cr, device=D), torch.zeros(Cr, C, device=D),
            torch.zeros(C, Cr, device=D)]
     L.call("hyres_se_bwd", y.data_ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
            hidden.data_ptr(), sgate.data_ptr(), gx32.data_ptr(), gws[0].data_ptr(), gws[1].data_ptr(), B, H * W, C, Cr,
-           ws.data_ptr(), ws.numel(), s)
-    L.call("hyres_se_bwd_f16", yh.data_ptr(), gh.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
+           ws.data_ptr(), ws.numel(), 0, s)
+    L.call("hyres_se_bwd", yh.data_ptr(), gh.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
            hidden.data_ptr(), sgate.data_ptr(), gx16.data_ptr(), gws[2].data_ptr(), gws[3].data_ptr(), B, H * W, C, Cr,
-           ws.data_ptr(), ws.numel(), 1, s)
+           ws.data_ptr(), ws.numel(), AG16, s)
     check(gx16, gx32, "se gx")
     assert rel_err(gws[2].cpu(), gws[0].cpu()) <= 1e-6 and rel_err(gws[3].cpu(), gws[1].cpu()) <= 1e-6
     wsa = _rand((1, 2, 7, 7), 7, 0.1).to(D)
@@ -243,19 +248,112 @@ def test_f16_gradient_backward_entry_points_match_rounded_fp32():
     attn = torch.empty(P, device=D)
     ysa = torch.empty(P, C, device=D)
     L.call("hyres_spatial_attn_fwd", y.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(),
-           attn.data_ptr(), ysa.data_ptr(), B, H, W, C, s)
+           attn.data_ptr(), ysa.data_ptr(), B, H, W, C, 0, s)
     gw32, gw16 = torch.zeros(1, 2, 7, 7, device=D), torch.zeros(1, 2, 7, 7, device=D)
     wsb = int(L.load().hyres_spatial_attn_workspace_bytes(B, H, W))
     ws = torch.empty(wsb, dtype=torch.uint8, device=D)
     L.call("hyres_spatial_attn_bwd", y.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(),
-           attn.data_ptr(), g.data_ptr(), gx32.data_ptr(), gw32.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(), s)
-    L.call("hyres_spatial_attn_bwd_f16", yh.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(),
-           attn.data_ptr(), gh.data_ptr(), gx16.data_ptr(), gw16.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(), 1,
-           s)
+           attn.data_ptr(), g.data_ptr(), gx32.data_ptr(), gw32.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(), 0, s)
+    L.call("hyres_spatial_attn_bwd", yh.data_ptr(), wsa.data_ptr(), pooled2.data_ptr(), amax.data_ptr(),
+           attn.data_ptr(), gh.data_ptr(), gx16.data_ptr(), gw16.data_ptr(), B, H, W, C, ws.data_ptr(), ws.numel(),
+           AG16, s)
     torch.cuda.synchronize()
     # the logit sums may contract differently (1 ulp): gx within one fp16 ulp of the rounded fp32 result
     assert (gx16.float() - gx32.half().float()).abs().max() <= 1e-3 * gx32.abs().max()
     assert rel_err(gw16.cpu(), gw32.cpu()) <= 1e-6
+
+
+def test_se_bwd_prelu_fp16_activations_fp32_gradients():
+    """hyres_se_bwd_prelu with HYRES_DT_ACT16 alone (fp16 x and pre-activation, fp32 gradients:
+    HYRES_AMP_F16_GRAD=0) against its fp32 form on the same fp16-representable values: gx and the weight gradients
+    bit for bit, the slope gradient (a sum of products) to 1e-6 — the criteria of the entry points above."""
+    from hyres_hip import _lib as L
+    D = dev()
+    B, H, W, C, Cr = 2, 16, 24, 64, 4
+    P = B * H * W
+    s = L.stream()
+    pre = _h(_rand((P, C), 11)).to(D)
+    x = _h(torch.where(pre > 0, pre, 0.25 * pre))
+    g = _rand((P, C), 12).to(D)
+    w1, w2 = _rand((Cr, C), 5, 0.2).to(D), _rand((C, Cr), 6, 0.2).to(D)
+    slope = torch.tensor([0.25], device=D)
+    pooled, hidden, sgate = (torch.empty(B, C, device=D), torch.empty(B, Cr, device=D), torch.empty(B, C, device=D))
+    yse = torch.empty(P, C, device=D)
+    ws = torch.empty(int(L.load().hyres_se_workspace_bytes(B, H * W, C)) + B * C * 4 + 2048 * 4, dtype=torch.uint8,
+                     device=D)
+    L.call("hyres_se_fwd", x.data_ptr(), w1.data_ptr(), w2.data_ptr(), yse.data_ptr(), pooled.data_ptr(),
+           hidden.data_ptr(), sgate.data_ptr(), B, H * W, C, Cr, ws.data_ptr(), ws.numel(), 0, s)
+    x16, pre16 = x.half(), pre.half()  # held for the calls
+    res = []
+    for xs, ps, dt in ((x16, pre16, L.DT_ACT16), (x, pre, 0)):
+        gx, gw1, gw2 = torch.empty(P, C, device=D), torch.zeros(Cr, C, device=D), torch.zeros(C, Cr, device=D)
+        dslope = torch.full((1,), 0.5, device=D)  # the slope gradient is ADDED
+        L.call("hyres_se_bwd_prelu", xs.data_ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), pooled.data_ptr(),
+               hidden.data_ptr(), sgate.data_ptr(), gx.data_ptr(), gw1.data_ptr(), gw2.data_ptr(), B, H * W, C, Cr,
+               ps.data_ptr(), slope.data_ptr(), dslope.data_ptr(), ws.data_ptr(), ws.numel(), dt, s)
+        torch.cuda.synchronize()
+        res.append((gx, gw1, gw2, dslope))
+    (gxh, gw1h, gw2h, dsh), (gxf, gw1f, gw2f, dsf) = res
+    print("se_bwd_prelu ACT16: gx mismatches", int((gxh != gxf).sum()), "dslope", dsh.item(), dsf.item())
+    assert bool((pre < 0).any()) and bool((pre > 0).any())
+    assert torch.equal(gxh, gxf) and torch.equal(gw1h, gw1f) and torch.equal(gw2h, gw2f)
+    assert rel_err(dsh.cpu(), dsf.cpu()) <= 1e-6
+
+
+@pytest.mark.parametrize("mask", ["act16", "grad16"])
+def test_bilinear_bwd_prelu_one_sided_masks(mask):
+    """hyres_bilinear_bwd_prelu with only the pre-activation fp16 (HYRES_DT_ACT16) or only the gradients fp16
+    (HYRES_DT_GRAD16) against its fp32 form on fp16-representable values (x2 up-sample, slope 0.25: scaling by it is
+    exact in fp16). ACT16: gx bit for bit, the slope gradient to 1e-6 (a sum of products). GRAD16: gx equals the fp32
+    result rounded to fp16 (the file's rounded-output criterion); the kernel rounds each gather sum g to fp16 BEFORE
+    the PReLU, so each term pre * g of the slope gradient carries a relative error <= 2^-11 (half an fp16 ulp):
+    |d16 - d32| <= 2^-11 * sum_{pre <= 0} |pre * g| + 1e-6 * |d32|."""
+    from hyres_hip import _lib as L
+    D = dev()
+    B, H, W, C = 2, 16, 24, 64
+    Ho, Wo = 2 * H, 2 * W
+    P = B * H * W
+    s = L.stream()
+    pre = _h(_rand((P, C), 21)).to(D)
+    gy = _h(_rand((B * Ho * Wo, C), 22)).to(D)
+    slope = torch.tensor([0.25], device=D)
+    ws = torch.empty(int(L.load().hyres_bilinear_bwd_prelu_workspace_bytes(B, H, W, C)), dtype=torch.uint8, device=D)
+    h_act, h_grad = mask == "act16", mask == "grad16"
+    res = []
+    for dt in (L.DT_ACT16 if h_act else L.DT_GRAD16, 0):
+        ps = pre.half() if dt and h_act else pre
+        gs = gy.half() if dt and h_grad else gy
+        gx = torch.empty(P, C, device=D, dtype=torch.float16 if dt and h_grad else torch.float32)
+        dslope = torch.full((1,), 0.5, device=D)  # ADDED to
+        L.call("hyres_bilinear_bwd_prelu", gs.data_ptr(), C, gx.data_ptr(), C, B, H, W, Ho, Wo, C, 0.5, 0.5,
+               ps.data_ptr(), C, slope.data_ptr(), dslope.data_ptr(), ws.data_ptr(), ws.numel(), dt, s)
+        torch.cuda.synchronize()
+        res.append((gx, dslope))
+    (gxm, dsm), (gxf, dsf) = res
+    print(mask, "dslope", dsm.item(), dsf.item())
+    assert bool((pre < 0).any()) and bool((pre > 0).any())
+    if h_act:
+        assert torch.equal(gxm, gxf)
+        assert rel_err(dsm.cpu(), dsf.cpu()) <= 1e-6
+    else:
+        _check_rounded(gxm, gxf, "bilinear_bwd_prelu gx")
+        neg = pre <= 0
+        bound = 2.0 ** -11 * float((pre[neg] * gxf[neg] / 0.25).abs().sum()) + 1e-6 * abs(dsf.item())
+        assert abs(dsm.item() - dsf.item()) <= bound, (dsm.item(), dsf.item(), bound)
+
+
+def test_accumulate_fp32():
+    """hyres_accumulate with f16 = 0 (y += x in fp32: one add per element, so exactly torch's), on the full and on a
+    ragged element count."""
+    from hyres_hip import _lib as L
+    D = dev()
+    n = 2 * 16 * 24 * 64
+    x, y0 = _rand((n,), 31).to(D), _rand((n,), 32).to(D)
+    for m in (n, n - 1):
+        y = y0.clone()
+        L.call("hyres_accumulate", x.data_ptr(), y.data_ptr(), m, 0, L.stream())
+        torch.cuda.synchronize()
+        assert torch.equal(y[:m], y0[:m] + x[:m]) and torch.equal(y[m:], y0[m:])
 
 
 # ------------------------------------------------------------------------------------------ conv layers
@@ -507,7 +605,7 @@ def _amp_head(fold, m, multi, gy, D):
 def test_refine_fusion_head_sa_fold_amp():
     """MultiScaleRefine's head (enhancement.py:105-109) in AMP training with fp16 activations and gradients: the
     SpatialAttention multiply folded into the fusion 1x1 (refine_ops.sa_fold_fusion's round-6 AMP build: ROWSCALE
-    forward on fp16 operands, hyres_sa_fold_bwd_f16, the SA_BWD epilogue on conv1x1_stream_hf_kernel) and unfused
+    forward on fp16 operands, hyres_sa_fold_bwd's fp16 form, the SA_BWD epilogue on conv1x1_stream_hf_kernel) and unfused
     (spatial_attention_mul + Sequential), each vs float64 torch without fp16 rounding: output, d multi and every
     parameter gradient within the AMP rounding (2e-2 max-norm; the slope, one cancelled sum, 5e-2; d multi 6e-2: the
     unfused chain measures 4.8e-2 on it here, the fold 4.7e-2 — fp16 gradients through the 7x7 map), and the fold
@@ -552,8 +650,8 @@ def test_refine_fusion_head_sa_fold_amp():
 
 @pytest.mark.parametrize("g16", [1, 0])
 def test_sa_fold_bwd_f16_matches_fp32_kernel(g16):
-    """hyres_sa_fold_bwd_f16 (fp16 pre-activation; fp16 or fp32 gy / gs) vs hyres_sa_fold_bwd on the same fp16-
-    representable values: gs within one fp16 rounding of the fp32 kernel's (1 ulp), glogit / d bias / d slope to fp32
+    """hyres_sa_fold_bwd with HYRES_DT_ACT16 (fp16 pre-activation; fp16 or fp32 gy / gs) vs its fp32 form on the same
+    fp16-representable values: gs within one fp16 rounding of the fp32 kernel's (1 ulp), glogit / d bias / d slope to fp32
     summation order (1e-5). A ragged pixel count, both PReLU sides, accumulation into existing d bias / d slope."""
     from hyres_hip import _lib as L
     D = dev()
@@ -573,13 +671,13 @@ def test_sa_fold_bwd_f16_matches_fp32_kernel(g16):
         db = torch.full((C,), 0.5, device=D)
         ds = torch.full((1,), 0.5, device=D)
         if f16:
-            L.call("hyres_sa_fold_bwd_f16", pre16.data_ptr(), C, gyc.data_ptr(), C, attn.data_ptr(),
+            L.call("hyres_sa_fold_bwd", pre16.data_ptr(), C, gyc.data_ptr(), C, attn.data_ptr(),
                    bias.data_ptr(), slope.data_ptr(), gs.data_ptr(), gl.data_ptr(), db.data_ptr(), ds.data_ptr(), P, C,
-                   ws.data_ptr(), ws.numel() * 4, g16, L.stream())
+                   ws.data_ptr(), ws.numel() * 4, L.DT_ACT16 | (L.DT_GRAD16 if g16 else 0), L.stream())
         else:
             L.call("hyres_sa_fold_bwd", pre.data_ptr(), C, gy.data_ptr(), C, attn.data_ptr(), bias.data_ptr(),
                    slope.data_ptr(), gs.data_ptr(), gl.data_ptr(), db.data_ptr(), ds.data_ptr(), P, C, ws.data_ptr(),
-                   ws.numel() * 4, L.stream())
+                   ws.numel() * 4, 0, L.stream())
         torch.cuda.synchronize()
         outs[name] = (gs.clone(), gl.clone(), db.clone(), ds.clone())
     (gs32, gl32, db32, ds32), (gs16, gl16, db16, ds16) = outs["f32"], outs["f16"]

@@ -46,6 +46,45 @@ def test_geometry_helpers_without_gpu():
     assert rc == 1001 and b"stride 2" in lib.hyres_last_error_string()
 
 
+DT_OPS = ["relu_bwd_2d", "prelu_bwd", "attn_gate_bwd", "attn_gate_bwd_relu", "gdn_dnorm", "se_bwd", "se_bwd_prelu",
+          "spatial_attn_bwd", "sa_fold_bwd"]  # ``int dt``: HYRES_DT_ACT16 | HYRES_DT_GRAD16
+F16_OPS = ["attn_gate_fwd", "accumulate", "colsum", "bilinear_fwd", "bilinear_bwd", "se_fwd", "spatial_attn_fwd"]
+BAD_DTYPE = ([(op, dt) for op in DT_OPS for dt in (2, 4, -1)]  # 2 = GRAD16 alone: no such kernel
+             + [(op, f16) for op in F16_OPS for f16 in (2, -1)]
+             + [("add2d", 4), ("add2d", -1), ("bilinear_bwd_prelu", 4), ("bilinear_bwd_prelu", -1)])
+
+
+@pytest.mark.parametrize("op,value", BAD_DTYPE)
+def test_entry_points_reject_a_dtype_without_a_kernel(op, value):
+    """The dtype argument (last before the stream) is checked before any pointer is looked at and before any launch:
+    a mask with no instantiation returns HYRES_E_ARG with a message naming the op, on dummy host pointers, no GPU."""
+    import ctypes
+    from hyres_hip import _lib as L
+    lib = L.load()
+    _, argtypes = L._SIGS["hyres_" + op]
+    buf = ctypes.create_string_buffer(64)
+    dummy = {ctypes.c_void_p: ctypes.addressof(buf), ctypes.c_int: 4, ctypes.c_longlong: 4, ctypes.c_float: 1.0}
+    args = [dummy[t] for t in argtypes]
+    assert argtypes[-2] is ctypes.c_int and argtypes[-1] is ctypes.c_void_p
+    args[-2], args[-1] = value, None
+    rc = getattr(lib, "hyres_" + op)(*args)
+    msg = lib.hyres_last_error_string().decode()
+    assert rc == 1003 and msg.startswith(op + ":"), (rc, msg)
+
+
+def test_dt_mask_helper():
+    import torch
+    from hyres_hip import _lib as L
+    h, f = torch.zeros(1, dtype=torch.float16), torch.zeros(1)
+    assert (L.DT_ACT16, L.DT_GRAD16) == (1, 2)
+    assert [L.dt_mask(a, g) for a, g in ((f, f), (h, f), (h, h), (f, h), (None, None))] == [0, 1, 3, 2, 0]
+    assert L.dt_mask(h, f, L.IO_X16, L.IO_AUX16) == L.IO_X16 and L.dt_mask(f, h, L.IO_X16, L.IO_AUX16) == L.IO_AUX16
+
+    class N:  # an ops.Node keeps its tensor in ``v``
+        v = h
+    assert L.dt_mask(N(), f) == L.DT_ACT16 and L.is_f16(N()) and not L.is_f16(None)
+
+
 def test_product_path_has_no_oracle_imports():
     pkg = os.path.join(REPO, "hyres-residual-enhanced-hybrid-image-compression_amd")
     offenders = []

@@ -717,13 +717,13 @@ def test_attn_gate_float4_and_relu_fold():
     x = _rand((P, C), 83).to(D)
     g = _rand((P, C), 84).to(D)
     out = torch.empty_like(a)
-    L.call("hyres_attn_gate_fwd", a.data_ptr(), b.data_ptr(), x.data_ptr(), out.data_ptr(), P * C, L.stream())
+    L.call("hyres_attn_gate_fwd", a.data_ptr(), b.data_ptr(), x.data_ptr(), out.data_ptr(), P * C, 0, L.stream())
     ga, gb, gam, gbm, gar = (torch.empty_like(a) for _ in range(5))
-    L.call("hyres_attn_gate_bwd", a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), P * C,
+    L.call("hyres_attn_gate_bwd", a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), P * C, 0,
            L.stream())
-    L.call("hyres_relu_bwd_2d", a.data_ptr(), C, ga.data_ptr(), C, gar.data_ptr(), C, P, C, L.stream())
+    L.call("hyres_relu_bwd_2d", a.data_ptr(), C, ga.data_ptr(), C, gar.data_ptr(), C, P, C, 0, L.stream())
     L.call("hyres_attn_gate_bwd_relu", a.data_ptr(), b.data_ptr(), g.data_ptr(), gam.data_ptr(), gbm.data_ptr(), P * C,
-           L.stream())
+           0, L.stream())
     torch.cuda.synchronize()
     s = torch.sigmoid(b.double())
     assert rel_err(out.double().cpu(), (a.double() * s + x.double()).cpu()) < 1e-6
@@ -736,8 +736,8 @@ def test_attn_gate_float4_and_relu_fold():
 @pytest.mark.parametrize("g16", [0, 1])
 def test_attn_gate_f16_vector_and_relu_fold(g16):
     """The AMP gate backward (fp16 a, b; fp16 or fp32 gradients) on the round-6 vector kernel equals the scalar kernel
-    (the one a ragged n runs on) bit for bit with fp32 gradients and within 1 fp16 ulp with fp16 ones, and the ReLU-folded variant (hyres_attn_gate_bwd_relu_f16) equals
-    the gate backward followed by hyres_relu_bwd_2d_f16 bit for bit."""
+    (the one a ragged n runs on) bit for bit with fp32 gradients and within 1 fp16 ulp with fp16 ones, and the ReLU-folded variant (hyres_attn_gate_bwd_relu) equals
+    the gate backward followed by hyres_relu_bwd_2d, both with the same dtype mask, bit for bit."""
     from hyres_hip import _lib as L
     D = dev()
     P, C = 8 * 32 * 32, 192
@@ -748,14 +748,15 @@ def test_attn_gate_f16_vector_and_relu_fold(g16):
     g = _rand((P, C), 93).to(D).to(gdt)
     ga, gb, gam, gbm, gar = (torch.empty(P, C, device=D, dtype=gdt) for _ in range(5))
     gas, gbs = (torch.zeros(P, C, device=D, dtype=gdt) for _ in range(2))
-    L.call("hyres_attn_gate_bwd_f16", a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), n, g16,
+    dt = L.DT_ACT16 | (L.DT_GRAD16 if g16 else 0)
+    L.call("hyres_attn_gate_bwd", a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), gb.data_ptr(), n, dt,
            L.stream())
     # n - 1: not a multiple of 4, the scalar kernel; the last element is compared separately below
-    L.call("hyres_attn_gate_bwd_f16", a.data_ptr(), b.data_ptr(), g.data_ptr(), gas.data_ptr(), gbs.data_ptr(), n - 1,
-           g16, L.stream())
-    L.call("hyres_relu_bwd_2d_f16", a.data_ptr(), C, ga.data_ptr(), C, gar.data_ptr(), C, P, C, g16, L.stream())
-    L.call("hyres_attn_gate_bwd_relu_f16", a.data_ptr(), b.data_ptr(), g.data_ptr(), gam.data_ptr(), gbm.data_ptr(), n,
-           g16, L.stream())
+    L.call("hyres_attn_gate_bwd", a.data_ptr(), b.data_ptr(), g.data_ptr(), gas.data_ptr(), gbs.data_ptr(), n - 1,
+           dt, L.stream())
+    L.call("hyres_relu_bwd_2d", a.data_ptr(), C, ga.data_ptr(), C, gar.data_ptr(), C, P, C, dt, L.stream())
+    L.call("hyres_attn_gate_bwd_relu", a.data_ptr(), b.data_ptr(), g.data_ptr(), gam.data_ptr(), gbm.data_ptr(), n,
+           dt, L.stream())
     torch.cuda.synchronize()
     if g16:
         # the scalar kernel's fp16 stores compile to v_fma_mixlo_f16 (product rounded once, straight to fp16: the
