@@ -1,7 +1,7 @@
 // Weight gradients (and bias column sums) for every Conv2d / ConvTranspose2d / GDN of the HyRES hot path on
 // CDNA4 (gfx950): dW[t][m][n] = sum_q P[q][m] * Q[shift_t(q)][n] over the batch's pixels, split-K over pixel
 // ranges into [nsplit][ntaps][M][N] slabs reduced in a fixed order (deterministic, no atomics).
-#include "conv_common.h"
+#include "wgrad_common.h"
 
 namespace hyres {
 
@@ -12,32 +12,9 @@ namespace hyres {
 //     and reused by all NT taps, only the shifted Q chunk is re-gathered per tap (L1/L2-hot);
 //   * ``tapn``: taps folded into the column dimension (c = t*N + n) for N <= 16 (3-channel images),
 //     so a 32-wide MFMA column tile is not 90% padding;
-//   * blocks of one pixel split are consecutive in logical order and mapped onto one XCD so their
-//     shared P/Q rows hit that XCD's L2;
+//   * blocks of one pixel split are consecutive in logical order and mapped onto one XCD (wgrad_logical_block);
 //   * split-K partials go to a [nsplit][ntaps][M][N] slab, reduced deterministically.
 // ------------------------------------------------------------------------------------------------
-struct WgradArgs {
-    hyres_wgrad_desc d;
-    const float* p;
-    const float* q;
-    float* slab;  // [nsplit][ntaps][M][N]
-    int chunks_per_split;
-    int nchunks;
-    int mtiles, ntiles, ngroups;
-    int nblocks;  // logical blocks (grid padded to a multiple of 8 for the XCD remap)
-    int tapn;
-    float* bias_slab;  // [nsplit][M] column sums of P (the bias gradient) or NULL
-};
-
-template <typename F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 template <int TM, int TN, int WAVES_M, int WAVES_N, int NT, bool VP, bool VQ, bool SQ>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     constexpr int BM = 32 * TM * WAVES_M;
@@ -52,16 +29,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     float* Qs = Qsm;
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x;
-    // XCD-aware order: hardware block b runs on XCD b % 8; give each XCD a contiguous logical range
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int grp = rr % a.ngroups;
-    const int split = rr / a.ngroups;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, true>(a, lb);
+    const int nt = blk.nt, grp = blk.grp, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const int t0 = grp * NT;
     const int HqWq = d.Hq * d.Wq;
     const long long Qtot = (long long)d.B * HqWq;
@@ -322,24 +293,12 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
             float* out = a.slab + ((long long)split * d.ntaps + t) * MN + n;
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (m < d.M) out[(long long)m * d.N] = acc[j][tm][tn][r];
-                }
+                slab_store_acc(acc[j][tm][tn], out, m0 + wm * TM * 32 + tm * 32, lh, d.M, d.N);
         }
     });
 }
 
 
-// ------------------------------------------------------------------------------------------------
-// Halo-staged weight gradient for KxK convolutions / transposed convolutions at Q stride SQ = 1 or 2 (K = 3:
-// one block does all 9 taps; K = 5: one kernel row of 5 taps per block) whose base rows are a multiple of
-// 32 pixels, so a 32-pixel K chunk is one row segment (b, i, j0..j0+31). Per chunk the block stages P
-// (32 px x 64 m) and ONE Q halo tile (KR rows x (31*SQ + K) px x 64 n) in LDS, double-buffered, and every
-// tap reads its B operand from the halo at its (dh, dw) shift (pixel k at column k*SQ + dw). The generic kernel instead gathers a shifted 32-px Q chunk per tap (9 global loads
-// and 9 barriers per chunk, the latency of each exposed at 2 blocks per CU); here it is one load of
-// 3 x 34 px per chunk and one barrier per 9 x 16 MFMAs. 64 x 64 tiles, 4 waves of 32 x 32.
 // ------------------------------------------------------------------------------------------------
 // 1x1 weight gradient (stride 1, fp32, 16B-aligned P/Q): dW[m][n] = sum_p P[p][m] Q[p][n] over the split's
 // pixel range. P and Q rows of one 32-pixel chunk are the same pixels, so both load as contiguous float4
@@ -373,14 +332,10 @@ __global__ __launch_bounds__(256 * G) void wgrad1x1_kernel(const WgradArgs a) {
         if constexpr (blocks == 2) asm volatile("" ::: "v127");
         else asm volatile("" ::: "v255");
     }
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int split = rr;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, false>(a, lb);
+    const int nt = blk.nt, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const long long Qtot = (long long)d.B * d.Hq * d.Wq;
     float4 rp[P_V], rq[Q_V];
     auto load = [&](int kc) {
@@ -566,6 +521,15 @@ __device__ __forceinline__ void combine_groups(floatx16 (&acc)[NT], float* red, 
     });
 }
 
+// ------------------------------------------------------------------------------------------------
+// Halo-staged weight gradient for KxK convolutions / transposed convolutions at Q stride SQ = 1 or 2 (K = 3:
+// one block does all 9 taps; K = 5: one kernel row of 5 taps per block) whose base rows are a multiple of
+// 32 pixels, so a 32-pixel K chunk is one row segment (b, i, j0..j0+31). Per chunk the block stages P
+// (32 px x 64 m) and ONE Q halo tile (KR rows x (31*SQ + K) px x 64 n) in LDS, double-buffered, and every
+// tap reads its B operand from the halo at its (dh, dw) shift (pixel k at column k*SQ + dw).
+// The generic kernel instead gathers a shifted 32-px Q chunk per tap (9 global loads
+// and 9 barriers per chunk, the latency of each exposed at 2 blocks per CU); here it is one load of
+// 3 x 34 px per chunk and one barrier per 9 x 16 MFMAs. 64 x 64 tiles, 4 waves of 32 x 32.
 // G = 2 (round 3): two 4-wave groups per 512-thread block share one pixel split (each its own contiguous half of
 // the split's chunks and its own LDS buffers: 1 block of 8 waves per CU instead of 2 of 4) and are summed through
 // LDS before the slab write, so the same waves write and the deferred reduce reads half the split slab.
@@ -583,15 +547,10 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(con
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x & 255, gq = threadIdx.x >> 8;
     float* const smem = smem_all + gq * (2 * (PSZ + HSZ));
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int grp = rr % a.ngroups;
-    const int split = rr / a.ngroups;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, true>(a, lb);
+    const int nt = blk.nt, grp = blk.grp, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const int t0 = grp * NT;
     const int dh0 = dhg + grp * KR * DIL;  // the group's first kernel row offset, first column offset dwg
     const int cpr = d.Wq / 32;
@@ -710,11 +669,7 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(con
         const int n = n0 + wn * 32 + lr;
         if (n < d.N) {
             float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < d.M) out[(long long)m * d.N] = acc[j][r];
-            }
+            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
         }
     });
 }
@@ -753,14 +708,6 @@ __device__ __forceinline__ half4_t q2h(const half4_t& v) { return v; }
 __device__ __forceinline__ half4_t q2h(const float4& v) {
     return half4_t{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
 }
-typedef __fp16 fp16x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 halfx4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 halfx8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ halfx4_t lds_tr4(const _Float16* p) {
-    fp16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_t*)(p));
-    return __builtin_bit_cast(halfx4_t, v);
-}
 
 // ONE: a 1x1 stride-1 gradient on the base grid (Q row = P row): Q rows load like P rows, no pixel decode.
 // IOH: operands stored fp16 in HBM (AMP training's saved activations): bit 0 P, bit 1 Q (8-byte loads of 4
@@ -775,15 +722,10 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const WgradArgs a) {
     __shared__ __attribute__((aligned(16))) _Float16 Qsm[2 * KTH * PQ];
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int grp = rr % a.ngroups;
-    const int split = rr / a.ngroups;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, true>(a, lb);
+    const int nt = blk.nt, grp = blk.grp, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const int t0 = grp * NT;
     const int HqWq = d.Hq * d.Wq;
     const long long Qtot = (long long)d.B * HqWq;
@@ -926,17 +868,11 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const WgradArgs a) {
             for (int s = 0; s < KTH / 16; ++s) {
                 halfx8_t af[TM], bf[TN];
 #pragma unroll
-                for (int tm = 0; tm < TM; ++tm) {
-                    const _Float16* src = Ps + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col;
-                    const halfx4_t lo = lds_tr4(src), hi = lds_tr4(src + 4 * PP);
-                    af[tm] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
+                for (int tm = 0; tm < TM; ++tm)
+                    af[tm] = tr_frag(Ps + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col, PP);
 #pragma unroll
-                for (int tn = 0; tn < TN; ++tn) {
-                    const _Float16* src = Qs + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col;
-                    const halfx4_t lo = lds_tr4(src), hi = lds_tr4(src + 4 * PQ);
-                    bf[tn] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
+                for (int tn = 0; tn < TN; ++tn)
+                    bf[tn] = tr_frag(Qs + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col, PQ);
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -1015,15 +951,10 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x & 255, gq = threadIdx.x >> 8;
     _Float16* const smem = smem_all + gq * (2 * (PSZ + HSZ));
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int grp = rr % a.ngroups;
-    const int split = rr / a.ngroups;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, true>(a, lb);
+    const int nt = blk.nt, grp = blk.grp, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const int t0 = grp * NT;
     const int dh0 = dhg + grp * KR * DIL;
     const int cpr = d.Wq / 32;
@@ -1099,15 +1030,12 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel
 #pragma unroll
         for (int s = 0; s < KT / 16; ++s) {
             if (kc >= ke) break;  // this group idles through the split's last step
-            const _Float16* pa = Ps + (16 * s + tr_row) * PP + wm * 32 + tr_col;
-            const halfx4_t alo = lds_tr4(pa), ahi = lds_tr4(pa + 4 * PP);
-            const halfx8_t af = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
+            const halfx8_t af = tr_frag(Ps + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
             static_for<NT>([&](auto J) {
                 constexpr int t = decltype(J)::value;
                 constexpr int hr = t / KW, hc = t % KW;
-                const _Float16* pb = Hs + (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col;
-                const halfx4_t blo = lds_tr4(pb), bhi = lds_tr4(pb + 4 * SQ * PQ);
-                const halfx8_t bf = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
+                const halfx8_t bf =
+                    tr_frag(Hs + (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col, SQ * PQ);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[t], 0, 0, 0);
             });
         }
@@ -1143,11 +1071,7 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel
         const int n = n0 + wn * 32 + lr;
         if (n < d.N) {
             float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < d.M) out[(long long)m * d.N] = acc[j][r];
-            }
+            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
         }
     });
 }
@@ -1171,14 +1095,10 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_kernel(const WgradArgs a) {
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int split = rr;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, false>(a, lb);
+    const int nt = blk.nt, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const long long Qtot = (long long)d.B * d.Hq * d.Wq;
     // fixed per-thread channel quads (256 % (B / 4) == 0): rows tid / (B / 4) + i * 256 / (B / 4)
     const int pc = (tid % (BM / 4)) * 4, prow0 = tid / (BM / 4);
@@ -1200,32 +1120,20 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_kernel(const WgradArgs a) {
     };
     const bool do_bias = a.bias_slab != nullptr && nt == 0;
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](__bf16* base, int o, const float4& v) {
-        bf16x4_t h, m, l;
-        bf6_split4(v, h, m, l);
-        *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
-        *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
-        *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
-    };
     auto store = [&](int buf) {
         __bf16* B0 = smem + buf * BUF;
 #pragma unroll
         for (int i = 0; i < P_V; ++i) {
             if (do_bias) { bsum.x += rp[i].x; bsum.y += rp[i].y; bsum.z += rp[i].z; bsum.w += rp[i].w; }
-            put(B0, (prow0 + i * PRS) * PP + pc, rp[i]);
+            bf6_put3<PLANE>(B0, (prow0 + i * PRS) * PP + pc, rp[i]);
         }
 #pragma unroll
-        for (int i = 0; i < Q_V; ++i) put(B0, PSZ + (qrow0 + i * QRS) * PQ + qc, rq[i]);
+        for (int i = 0; i < Q_V; ++i) bf6_put3<PLANE>(B0, PSZ + (qrow0 + i * QRS) * PQ + qc, rq[i]);
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
     const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
-    auto frag = [&](const __bf16* p, int pitch) {
-        const halfx4_t lo = lds_tr4(reinterpret_cast<const _Float16*>(p));
-        const halfx4_t hi = lds_tr4(reinterpret_cast<const _Float16*>(p + 4 * pitch));
-        return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
     floatx16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -1253,12 +1161,14 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_kernel(const WgradArgs a) {
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    af[tm][pl] = frag(Ps + pl * PLANE + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col, PP);
+                    af[tm][pl] =
+                        tr_frag(Ps + pl * PLANE + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col, PP);
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    bf[tn][pl] = frag(Qs + pl * PLANE + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col, PQ);
+                    bf[tn][pl] =
+                        tr_frag(Qs + pl * PLANE + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col, PQ);
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -1326,14 +1236,10 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int split = rr;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, false>(a, lb);
+    const int nt = blk.nt, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const long long Qtot = (long long)d.B * d.Hq * d.Wq;
     const int pc = (tid % (BM / 4)) * 4, prow0 = tid / (BM / 4);
     const int qc = (tid % (BN / 4)) * 4, qrow0 = tid / (BN / 4);
@@ -1360,32 +1266,20 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
     };
     const bool do_bias = a.bias_slab != nullptr && nt == 0;
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](__bf16* base, int o, const float4& v) {
-        bf16x4_t h, m, l;
-        bf6_split4(v, h, m, l);
-        *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
-        *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
-        *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
-    };
     auto store = [&](int buf, const float4 (&rp)[P_V], const float4 (&rq)[Q_V]) {
         __bf16* B0 = smem + buf * BUF;
 #pragma unroll
         for (int i = 0; i < P_V; ++i) {
             if (do_bias) { bsum.x += rp[i].x; bsum.y += rp[i].y; bsum.z += rp[i].z; bsum.w += rp[i].w; }
-            put(B0, (prow0 + i * PRS) * PP + pc, rp[i]);
+            bf6_put3<PLANE>(B0, (prow0 + i * PRS) * PP + pc, rp[i]);
         }
 #pragma unroll
-        for (int i = 0; i < Q_V; ++i) put(B0, PSZ + (qrow0 + i * QRS) * PQ + qc, rq[i]);
+        for (int i = 0; i < Q_V; ++i) bf6_put3<PLANE>(B0, PSZ + (qrow0 + i * QRS) * PQ + qc, rq[i]);
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
     const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
-    auto frag = [&](const __bf16* p, int pitch) {
-        const halfx4_t lo = lds_tr4(reinterpret_cast<const _Float16*>(p));
-        const halfx4_t hi = lds_tr4(reinterpret_cast<const _Float16*>(p + 4 * pitch));
-        return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
     floatx16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -1413,12 +1307,14 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                 for (int pl3 = 0; pl3 < 3; ++pl3)
-                    af[tm][pl3] = frag(Ps + pl3 * PLANE + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col, PP);
+                    af[tm][pl3] =
+                        tr_frag(Ps + pl3 * PLANE + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col, PP);
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
                 for (int pl3 = 0; pl3 < 3; ++pl3)
-                    bf[tn][pl3] = frag(Qs + pl3 * PLANE + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col, PQ);
+                    bf[tn][pl3] =
+                        tr_frag(Qs + pl3 * PLANE + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col, PQ);
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -1486,15 +1382,10 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int grp = rr % a.ngroups;
-    const int split = rr / a.ngroups;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, true>(a, lb);
+    const int nt = blk.nt, grp = blk.grp, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const int t0 = grp * NT;
     const int dh0 = dhg + grp * KR * DIL;
     const int cpr = d.Wq / 32;
@@ -1522,24 +1413,17 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
     };
     const bool do_bias = a.bias_slab != nullptr && nt == 0 && grp == 0;
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](__bf16* base, int o, const float4& v) {
-        bf16x4_t h, m, l;
-        bf6_split4(v, h, m, l);
-        *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
-        *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
-        *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
-    };
     auto store = [&](int buf) {
         __bf16* B0 = smem + buf * BUF;
 #pragma unroll
         for (int q = 0; q < P_V; ++q) {
             if (do_bias) { bsum.x += rp[q].x; bsum.y += rp[q].y; bsum.z += rp[q].z; bsum.w += rp[q].w; }
-            put(B0, (prow0 + 16 * q) * PP + pc, rp[q]);
+            bf6_put3<PLANE>(B0, (prow0 + 16 * q) * PP + pc, rp[q]);
         }
 #pragma unroll
         for (int q = 0; q < H_V; ++q) {
             const int e = tid + 256 * q;
-            if (e < H_E) put(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
+            if (e < H_E) bf6_put3<PLANE>(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
         }
     };
 
@@ -1548,11 +1432,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
     // transposed-read lane address (wgrad_f16_kernel): half lh takes k rows 8lh..8lh+7 of a 16-k step
     const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
     const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
-    auto frag = [&](const __bf16* p, int pitch) {  // 8 consecutive k of one row / column, transposed read
-        const halfx4_t lo = lds_tr4(reinterpret_cast<const _Float16*>(p));
-        const halfx4_t hi = lds_tr4(reinterpret_cast<const _Float16*>(p + 4 * pitch));
-        return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
     floatx16 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -1575,14 +1454,14 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
         for (int s = 0; s < KT / 16; ++s) {
             bf16x8_t af[3];
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) af[pl] = frag(Ps + pl * PLANE + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
+            for (int pl = 0; pl < 3; ++pl) af[pl] = tr_frag(Ps + pl * PLANE + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
             static_for<NT>([&](auto J) {
                 constexpr int t = decltype(J)::value;
                 constexpr int hr = t / KW, hc = t % KW;
                 const int ob = (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col;
                 bf16x8_t bf[3];
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) bf[pl] = frag(Hs + pl * PLANE + ob, SQ * PQ);
+                for (int pl = 0; pl < 3; ++pl) bf[pl] = tr_frag(Hs + pl * PLANE + ob, SQ * PQ);
                 acc[t] = bf6_mfma(af, bf, acc[t]);
             });
         }
@@ -1613,11 +1492,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
         const int n = n0 + wn * 32 + lr;
         if (n < d.N) {
             float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < d.M) out[(long long)m * d.N] = acc[j][r];
-            }
+            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
         }
     });
 }
@@ -1646,15 +1521,10 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int bid = blockIdx.x;
-    const int lb = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-aware order, as wgrad_kernel
+    const int lb = wgrad_logical_block();
     if (lb >= a.nblocks) return;
-    int rr = lb;
-    const int mt = rr % a.mtiles; rr /= a.mtiles;
-    const int nt = rr % a.ntiles; rr /= a.ntiles;
-    const int grp = rr % a.ngroups;
-    const int split = rr / a.ngroups;
-    const int m0 = mt * BM, n0 = nt * BN;
+    const WgradBlock blk = wgrad_block<BM, BN, true>(a, lb);
+    const int nt = blk.nt, grp = blk.grp, split = blk.split, m0 = blk.m0, n0 = blk.n0;
     const int t0 = grp * NT;
     const int dh0 = dhg + grp * KR * DIL;
     const int cpr = d.Wq / 32;
@@ -1692,35 +1562,23 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
     };
     const bool do_bias = a.bias_slab != nullptr && nt == 0 && grp == 0;
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](__bf16* base, int o, const float4& v) {
-        bf16x4_t h, m, l;
-        bf6_split4(v, h, m, l);
-        *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
-        *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
-        *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
-    };
     auto store = [&](int buf, const float4 (&rp)[P_V], const float4 (&rh)[H_V]) {
         __bf16* B0 = smem + buf * BUF;
 #pragma unroll
         for (int q = 0; q < P_V; ++q) {
             if (do_bias) { bsum.x += rp[q].x; bsum.y += rp[q].y; bsum.z += rp[q].z; bsum.w += rp[q].w; }
-            put(B0, (prow0 + 16 * q) * PP + pc, rp[q]);
+            bf6_put3<PLANE>(B0, (prow0 + 16 * q) * PP + pc, rp[q]);
         }
 #pragma unroll
         for (int q = 0; q < H_V; ++q) {
             const int e = tid + 256 * q;
-            if (e < H_E) put(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
+            if (e < H_E) bf6_put3<PLANE>(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
         }
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
     const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
-    auto frag = [&](const __bf16* p, int pitch) {
-        const halfx4_t lo = lds_tr4(reinterpret_cast<const _Float16*>(p));
-        const halfx4_t hi = lds_tr4(reinterpret_cast<const _Float16*>(p + 4 * pitch));
-        return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
     floatx16 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -1743,14 +1601,14 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
             bf16x8_t af[3];
 #pragma unroll
             for (int pl3 = 0; pl3 < 3; ++pl3)
-                af[pl3] = frag(Ps + pl3 * PLANE + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
+                af[pl3] = tr_frag(Ps + pl3 * PLANE + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
             static_for<NT>([&](auto J) {
                 constexpr int t = decltype(J)::value;
                 constexpr int hr = t / KW, hc = t % KW;
                 const int ob = (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col;
                 bf16x8_t bf[3];
 #pragma unroll
-                for (int pl3 = 0; pl3 < 3; ++pl3) bf[pl3] = frag(Hs + pl3 * PLANE + ob, SQ * PQ);
+                for (int pl3 = 0; pl3 < 3; ++pl3) bf[pl3] = tr_frag(Hs + pl3 * PLANE + ob, SQ * PQ);
                 acc[t] = bf6_mfma(af, bf, acc[t]);
             });
         }
@@ -1784,11 +1642,7 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
         const int n = n0 + wn * 32 + lr;
         if (n < d.N) {
             float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < d.M) out[(long long)m * d.N] = acc[j][r];
-            }
+            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
         }
     });
 }
