@@ -84,6 +84,33 @@ MSSSIM_HD void ssim_pixel(const float m[5], const Consts& c, float& cs, float& s
     ssim = ((2.0f * mu12 + c.C1) / (mu1_sq + mu2_sq + c.C1)) * cs;
 }
 
+// The backward of one filter output p towards the second image: with g the window weight that joins p to the input
+// pixel q, d cs(p) / d y(q) = g * (x(q) * a + y(q) * b + c) where a = 2 / B2, b = -cs * a, c = a * (cs * mu2 - mu1)
+// and B2 = s1 + s2 + C2. ``last`` gives the same three coefficients for ssim(p) = l * cs: l times the above, plus
+// cs * dl / dmu2 = cs * 2 * (mu1 - l * mu2) / B1 in c.
+MSSSIM_HD void ssim_pixel_bwd(const float m[5], const Consts& k, bool last, float& a, float& b, float& c) {
+    const float mu1 = m[0], mu2 = m[1];
+    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+    const float s1 = m[2] - mu1_sq, s2 = m[3] - mu2_sq, s12 = m[4] - mu12;
+    const float B2 = s1 + s2 + k.C2;
+    const float cs = (2.0f * s12 + k.C2) / B2;
+    a = 2.0f / B2;
+    b = -cs * a;
+    c = a * (cs * mu2 - mu1);
+    if (last) {
+        const float B1 = mu1_sq + mu2_sq + k.C1;
+        const float l = (2.0f * mu12 + k.C1) / B1;
+        a *= l, b *= l;
+        c = fmaf(l, c, cs * (2.0f * (mu1 - l * mu2) / B1));
+    }
+}
+
+// the level's local gradient at input pixel q from the transposed-filtered coefficient maps, times the upstream
+// factor ``u`` of this (level, image, channel); exactly 0 where u is 0
+MSSSIM_HD float grad_pixel(float x, float y, float ta, float tb, float tc, float u) {
+    return u == 0.0f ? 0.0f : u * fmaf(x, ta, fmaf(y, tb, tc));
+}
+
 // avg_pool2d(kernel 2, stride 2, padding = side % 2, count_include_pad): the next level's side
 MSSSIM_HD int pooled_size(int s) { return (s + 2 * (s & 1) - 2) / 2 + 1; }
 
@@ -103,6 +130,10 @@ MSSSIM_HD float pool_pixel(int H, int W, int j, int i, At at) {
     return acc * 0.25f;
 }
 
+// the transpose of pool_pixel: row / column r of a plane of side ``side`` lies in the window of pooled row / column
+// (r + side % 2) / 2, which always exists; the padded positions have no pixel and so receive nothing
+MSSSIM_HD int pool_parent(int side, int r) { return (r + (side & 1)) >> 1; }
+
 // prod_l relu(mean[l])^w[l] in fp64; mean[l * stride] = the raw spatial mean of level l (cs, or ssim for the last)
 MSSSIM_HD double combine(const double* mean, long long stride, const Weights& w, int levels) {
     double p = 1.0;
@@ -111,6 +142,15 @@ MSSSIM_HD double combine(const double* mean, long long stride, const Weights& w,
         p *= pow(v, (double)w.w[l]);
     }
     return p;
+}
+
+// d combine / d mean[l] = w[l] * combine / mean[l] in fp64, and exactly 0 for every level as soon as one level's mean
+// is <= 0 (what relu's and pow's backward give: never inf or NaN)
+MSSSIM_HD void combine_bwd(const double* mean, long long stride, const Weights& w, int levels, double d[kMaxLevels]) {
+    bool pos = true;
+    for (int l = 0; l < levels; ++l) pos = pos && mean[l * stride] > 0.0;
+    const double p = pos ? combine(mean, stride, w, levels) : 0.0;
+    for (int l = 0; l < levels; ++l) d[l] = pos ? (double)w.w[l] * p / mean[l * stride] : 0.0;
 }
 
 // min(H, W) must exceed this for ``levels`` levels: every level keeps at least one filter output

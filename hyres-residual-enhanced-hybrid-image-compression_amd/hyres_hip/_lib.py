@@ -144,6 +144,9 @@ _SIGS = {
     "hyres_msssim_workspace_bytes": (_LL, [_I, _I, _I, _I, _I]),
     "hyres_msssim": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),
     "hyres_msssim_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),
+    "hyres_msssim_bwd_workspace_bytes": (_LL, [_I, _I, _I, _I, _I]),
+    "hyres_msssim_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),
+    "hyres_msssim_bwd_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),
     "hyres_ckbd_anchor_fwd":(_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "hyres_ckbd_nonanchor_gc_fwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                          _I, _I, _I, _I, _P]),

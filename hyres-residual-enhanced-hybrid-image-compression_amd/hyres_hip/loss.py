@@ -4,7 +4,11 @@ The bpp log-sums and the MSE are deterministic two-pass block reductions; the si
 finalised on device (no host sync).  The VGG16 perceptual term (rd_loss.py:40, alpha * vgg * 255^2) runs
 on the HIP path (hyres_hip.vgg.VGGLoss) when alpha != 0; its ImageNet weights must be available locally
 (HYRES_VGG16_WEIGHTS).  With alpha = 0 (train.sh:14) it is not evaluated — the reference computes it and
-multiplies it by zero."""
+multiplies it by zero.
+
+``metric="ms-ssim"`` (compressai's RateDistortionLoss convention) trains for MS-SSIM instead of MSE:
+loss = lmbda * (1 - ms_ssim(x_hat, target, data_range=1)) + bpp_loss, with the HIP forward and backward of
+hyres_hip.metrics; ``metric="mse"``, the default, never imports or calls the metric."""
 from __future__ import annotations
 
 import torch
@@ -67,10 +71,15 @@ class _RDLossFn(torch.autograd.Function):
 class RateDistortionLoss(nn.Module):
     """Custom rate distortion loss with a Lagrangian parameter (src/losses/rd_loss.py)."""
 
-    def __init__(self, lmbda=0.004, alpha=0.001, vgg=None):
+    METRICS = ("mse", "ms-ssim")
+
+    def __init__(self, lmbda=0.004, alpha=0.001, vgg=None, metric="mse"):
         super().__init__()
+        if metric not in self.METRICS:
+            raise ValueError(f"RateDistortionLoss: metric must be one of {self.METRICS} (got {metric!r})")
         self.lmbda = lmbda
         self.alpha = alpha
+        self.metric = metric
         if alpha != 0 and vgg is None:
             from .vgg import VGGLoss
             vgg = VGGLoss()  # ImageNet weights from HYRES_VGG16_WEIGHTS (raises when absent)
@@ -80,10 +89,15 @@ class RateDistortionLoss(nn.Module):
         lik = output["likelihoods"]
         loss, bpp, res, yb, zb, mse = _RDLossFn.apply(lik["y"], lik["z"], output["x_hat"], target,
                                                       output.get("jpeg_bpp_loss"), self.lmbda)
+        extra = {}
+        if self.metric == "ms-ssim":
+            from .metrics import ms_ssim
+            extra["ms_ssim_loss"] = 1 - ms_ssim(output["x_hat"], target, data_range=1.0)
+            loss = self.lmbda * extra["ms_ssim_loss"] + bpp  # the MSE is reported, not optimised
         if self.alpha != 0:
             vgg = self.vgg(output["x_hat"], target) * 255 ** 2  # rd_loss.py:40
             loss = loss + self.alpha * vgg                      # rd_loss.py:42
         else:
             vgg = torch.zeros((), device=target.device)
         return {"loss": loss, "bpp_loss": bpp, "residual_bpp_loss": res, "y_bpp_loss": yb, "z_bpp_loss": zb,
-                "mse_loss": mse, "vgg_loss": vgg}
+                "mse_loss": mse, "vgg_loss": vgg, **extra}

@@ -51,7 +51,19 @@ def parse_args(argv):
     p.add_argument("--gpu-id", default="0", type=str, help="id(s) for CUDA_VISIBLE_DEVICES")
     p.add_argument("--savepath", default="./checkpoint", type=str, help="Path to save the checkpoint")
     p.add_argument("--checkpoint", type=str, help="Path to a checkpoint")
-    return p.parse_args(argv)
+    p.add_argument("--metric", choices=("mse", "ms-ssim"), default="mse",
+                   help="Distortion the loss optimises (default: %(default)s)")
+    args = p.parse_args(argv)
+    check_metric(args)
+    return args
+
+
+def check_metric(args):
+    """Five-level MS-SSIM keeps a filter output at its coarsest level only above 160 pixels a side: refuse the run
+    before any data is touched."""
+    if args.metric == "ms-ssim" and min(args.patch_size) <= 160:
+        raise SystemExit(f"--metric ms-ssim: min(--patch-size) must be larger than 160 = (11 - 1) * 2^4 "
+                         f"(got {args.patch_size[0]} x {args.patch_size[1]})")
 
 
 class _NullWriter:
@@ -125,7 +137,7 @@ def main(argv):
         names = sorted(n for n, p in net.named_parameters() if not n.endswith(".quantiles") and p.requires_grad)
         reducer = FlatGradReducer(optimizer.flat, world, names=names, segments=HYRES_SEGMENTS).overlap()
     lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[400], gamma=0.1)
-    criterion = RateDistortionLoss(lmbda=args.lmbda, alpha=args.alpha)
+    criterion = RateDistortionLoss(lmbda=args.lmbda, alpha=args.alpha, metric=args.metric)
 
     last_epoch = 0
     if args.checkpoint:

@@ -649,6 +649,21 @@ int hyres_msssim(const float* x, const float* y, int B, int C, int H, int W, int
 int hyres_msssim_host(const float* x, const float* y, int B, int C, int H, int W, int levels, const float* weights,
                       float data_range, float* out, float* per_level, void* ws, long long ws_bytes,
                       hyres_stream_t s);
+/* workspace of hyres_msssim_bwd, or -1 on a bad shape (host) */
+long long hyres_msssim_bwd_workspace_bytes(int B, int C, int H, int W, int levels);
+/* grad_y [B,C,H,W] = d (sum_b grad_out[b] * out[b]) / d y for the ``out`` of hyres_msssim on the same arguments;
+ * grad_out: B floats on the device. The function is symmetric in x and y: the gradient towards x is the same call with
+ * the two images swapped. Self-contained: it runs hyres_msssim's launches again into its own workspace, then one
+ * small kernel and two kernels per level (3 * levels + 2 launches). A channel in which any level's mean is <= 0 gets
+ * exactly 0. Gather only; no host sync, allocation, copy, memset or atomic, every sum in a fixed order: capture-legal,
+ * and the same input gives the same bits, alone or inside a batch. */
+int hyres_msssim_bwd(const float* x, const float* y, int B, int C, int H, int W, int levels, const float* weights,
+                     float data_range, const float* grad_out, float* grad_y, void* ws, long long ws_bytes,
+                     hyres_stream_t s);
+/* the same on host memory with the same arithmetic; ws and s are ignored, no GPU call is made (host) */
+int hyres_msssim_bwd_host(const float* x, const float* y, int B, int C, int H, int W, int levels,
+                          const float* weights, float data_range, const float* grad_out, float* grad_y, void* ws,
+                          long long ws_bytes, hyres_stream_t s);
 
 #ifdef __cplusplus
 }
