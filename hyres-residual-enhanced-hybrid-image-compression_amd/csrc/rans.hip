@@ -9,6 +9,7 @@
 // inherently sequential per stream (one string per image), so it stays on the host; the per-element work
 // around it (CDF index building, symbolisation, dequantisation) runs in HIP kernels (entropy.hip).
 #include "common.h"
+#include "wrans_core.h"
 
 #include <cmath>
 #include <cstdint>
@@ -18,8 +19,8 @@
 namespace hyres {
 namespace rans {
 
-constexpr uint64_t RANS64_L = 1ull << 31;  // lower bound of the normalisation interval (64-bit state)
-constexpr int PRECISION = 16;
+constexpr uint64_t RANS64_L = wrans::kL;  // lower bound of the normalisation interval (64-bit state)
+constexpr int PRECISION = wrans::kPrecision;
 constexpr int BYPASS_PRECISION = 4;
 constexpr int MAX_BYPASS_VAL = (1 << BYPASS_PRECISION) - 1;
 
@@ -28,17 +29,14 @@ struct Sym {
     bool bypass;
 };
 
-// 64-bit state, 32-bit output words written backwards (ryg_rans rans64 as used by compressai)
+// 64-bit state, 32-bit output words written backwards (ryg_rans rans64 as used by compressai); the step arithmetic
+// is wrans_core.h's, shared with the device coder
 struct Enc {
     uint64_t x = RANS64_L;
     std::vector<uint32_t> rev;  // words in reverse output order
     void put(uint32_t start, uint32_t freq, int scale_bits) {
-        const uint64_t x_max = ((RANS64_L >> scale_bits) << 32) * freq;
-        if (x >= x_max) {
-            rev.push_back((uint32_t)x);
-            x >>= 32;
-        }
-        x = ((x / freq) << scale_bits) + (x % freq) + start;
+        uint32_t word;
+        if (wrans::enc_put(x, start, freq, scale_bits, word)) rev.push_back(word);
     }
     void put_bits(uint32_t val, int nbits) {  // compressai Rans64EncPutBits (nbits <= 16)
         const uint32_t freq = 1u << (16 - nbits);
@@ -66,11 +64,9 @@ struct Dec {
         x = (uint64_t)next();
         x |= (uint64_t)next() << 32;
     }
-    uint32_t get(int scale_bits) const { return (uint32_t)(x & ((1u << scale_bits) - 1)); }
+    uint32_t get(int scale_bits) const { return wrans::dec_get(x, scale_bits); }
     void advance(uint32_t start, uint32_t freq, int scale_bits) {
-        const uint64_t mask = (1ull << scale_bits) - 1;
-        x = freq * (x >> scale_bits) + (x & mask) - start;
-        if (x < RANS64_L) x = (x << 32) | next();
+        if (wrans::dec_advance(x, start, freq, scale_bits)) wrans::dec_refill(x, next());
     }
     uint32_t get_bits(int nbits) {
         const uint32_t v = (uint32_t)(x & ((1u << nbits) - 1));
@@ -199,13 +195,7 @@ int hyres_rans_decode_with_indexes(const unsigned char* in, long long in_len, co
         const uint32_t cum = dec.get(rans::PRECISION);
         // s with cdf[s] <= cum < cdf[s+1] (compressai scans linearly; the CDF is strictly increasing, so a
         // binary search finds the same s in O(log L) — wide scales have L in the thousands)
-        int lo = 0, hi = max_value;  // cdf[max_value + 1] = 2^16 > cum
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if ((uint32_t)cdf[mid] <= cum) lo = mid;
-            else hi = mid - 1;
-        }
-        const int s = lo;
+        const int s = wrans::cdf_search(cdf, max_value, cum);  // cdf[max_value + 1] = 2^16 > cum
         dec.advance((uint32_t)cdf[s], (uint32_t)(cdf[s + 1] - cdf[s]), rans::PRECISION);
         int value = s;
         if (value == max_value) {

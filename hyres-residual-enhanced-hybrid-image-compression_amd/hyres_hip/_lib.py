@@ -136,6 +136,14 @@ _SIGS = {
     "hyres_pmf_to_quantized_cdf": (_I, [_P, _I, _I, _P]),
     "hyres_rans_encode_with_indexes": (_I, [_P, _P, _LL, _P, _I, _P, _P, _I, _P, _LL, ctypes.POINTER(_LL)]),
     "hyres_rans_decode_with_indexes": (_I, [_P, _LL, _P, _LL, _P, _I, _P, _P, _I, _P]),
+    "hyres_wrans_count": (_LL, [_I, _I, _I, _I]),
+    "hyres_wrans_max_string_bytes": (_LL, [_I, _I, _I, _I]),
+    "hyres_wrans_workspace_bytes": (_LL, [_I, _I, _I, _I, _I]),
+    "hyres_wrans_encode": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _LL, _P, _I, _P, _LL, _P]),
+    "hyres_wrans_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "hyres_wrans_validate": (_I, [_P, _LL, _I, _I, _I, _I]),
+    "hyres_wrans_encode_host": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _LL, ctypes.POINTER(_LL)]),
+    "hyres_wrans_decode_host": (_I, [_P, _LL, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "hyres_jpeg_quant_tables": (_I, [_I, _P, _P]),
     "hyres_jpeg_workspace_bytes": (_LL, [_I, _I, _I]),
     "hyres_jpeg_stream_bytes": (_LL, [_I, _I]),

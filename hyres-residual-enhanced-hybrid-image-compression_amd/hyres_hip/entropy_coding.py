@@ -10,6 +10,11 @@
   (``hyres_eb_symbols``, ``hyres_gc_symbols``, ``hyres_gc_dequant``) on the NHWC activations; the
   sequential rANS coder (one string per image, compressai's wire format) runs on the host
   (``hyres_rans_encode_with_indexes`` / ``hyres_rans_decode_with_indexes``).
+* Opt-in device coder (``LightWeightCheckerboard.device_coder``, HYRES_ENTROPY_CODER=device): ``DeviceEncoder`` /
+  ``DeviceDecoder`` code the same symbols with the wave-interleaved format HRW1 (csrc/wrans.hip, one wave per
+  string, its own wire format: DESIGN.md "Device rANS coder"). Symbols and indexes stay on the device: compress
+  downloads the offset table and the packed bytes, decompress uploads all strings of the call once and queues its
+  decode launches on the stream without a host wait.
 """
 from __future__ import annotations
 
@@ -77,7 +82,7 @@ def eb_update(eb, force: bool = False) -> bool:
     eb._offset = (-minima).to(dev)
     eb._quantized_cdf = _pmf_to_cdf(pmf, tail_mass, pmf_length, max_length).to(dev)
     eb._cdf_length = (pmf_length + 2).to(dev)
-    eb._coder_cache = None
+    eb._coder_cache = eb._coder_cache_dev = None
     return True
 
 
@@ -108,7 +113,7 @@ def gc_update(gc) -> None:
     gc._quantized_cdf = _pmf_to_cdf(pmf, tail_mass, pmf_length, max_length).to(dev)
     gc._offset = (-pmf_center).to(dev)
     gc._cdf_length = (pmf_length + 2).to(dev)
-    gc._coder_cache = None
+    gc._coder_cache = gc._coder_cache_dev = None
 
 
 def _tables(model):
@@ -260,3 +265,178 @@ def gc_decompress(gc, strings: List[bytes], params: Node, M: int, out: Node, acc
 def get_scale_table(min_=0.11, max_=256, levels=64):
     """models/checkerboard.py:17-21."""
     return torch.exp(torch.linspace(math.log(min_), math.log(max_), levels))
+
+
+# ------------------------------------------------------------------------------------------ device coder (HRW1)
+CODERS = ("host", "device")
+WRANS_MAGIC = b"HRW1"
+
+
+def coder_from_env() -> bool:
+    """HYRES_ENTROPY_CODER=host|device (default host) -> the ``device_coder`` switch; anything else is refused."""
+    import os
+    coder = os.environ.get("HYRES_ENTROPY_CODER", "host")
+    if coder not in CODERS:
+        raise ValueError(f"HYRES_ENTROPY_CODER={coder!r}: 'host' or 'device'")
+    return coder == "device"
+
+
+def _tables_dev(model, device):
+    """Device-resident int32 copies of a model's CDF tables, sizes and offsets (cached until the next update)."""
+    c = getattr(model, "_coder_cache_dev", None)
+    if c is None or c[0] != device:
+        if model._offset.numel() == 0:
+            raise ValueError("Entropy coder tables are not initialised: run model.update() first "
+                             "(compressai: 'Uninitialized CDFs. Run update() first')")
+        c = (device, model._quantized_cdf.to(device=device, dtype=torch.int32).contiguous(),
+             model._cdf_length.to(device=device, dtype=torch.int32).contiguous(),
+             model._offset.to(device=device, dtype=torch.int32).contiguous())
+        model._coder_cache_dev = c
+    return c[1:]
+
+
+def _table_args(tables):
+    cdf, lengths, offsets = tables
+    return cdf.data_ptr(), cdf.shape[1], lengths.data_ptr(), offsets.data_ptr(), cdf.shape[0]
+
+
+def wrans_count(C: int, H: int, W: int, parity: int) -> int:
+    n = L.load().hyres_wrans_count(C, H, W, parity)
+    if n < 0:
+        raise ValueError(f"wrans: bad latent shape C={C} H={H} W={W} parity={parity}")
+    return int(n)
+
+
+def wrans_max_string_bytes(C: int, H: int, W: int, parity: int) -> int:
+    return 528 + 8 * wrans_count(C, H, W, parity)
+
+
+def wrans_validate(data: bytes, C: int, H: int, W: int, parity: int) -> None:
+    """ValueError unless ``data`` is an HRW1 string of a [C,H,W] latent under ``parity`` (host check, no launch)."""
+    lib = L.load()
+    if lib.hyres_wrans_validate(data, len(data), C, H, W, parity) != 0:
+        raise ValueError(lib.hyres_last_error_string().decode())
+
+
+class DeviceEncoder:
+    """The strings of one compress call: every ``add`` queues an encode + pack launch pair that appends its B
+    strings to one device buffer and one offset table (chained on the stream); ``finish`` downloads the offset
+    table, then the used prefix of the buffer, and returns the strings group by group."""
+
+    def __init__(self, device, groups):
+        """``groups``: (B, C, H, W, parity) of every ``add`` to come, in order (sizes the buffer once)."""
+        self.device = device
+        self.groups = list(groups)
+        cap = sum(B * wrans_max_string_bytes(C, H, W, p) for B, C, H, W, p in self.groups)
+        self.out = torch.empty(cap, dtype=torch.uint8, device=device)
+        self.offs = torch.empty(sum(g[0] for g in self.groups) + 1, dtype=torch.int64, device=device)
+        self.done = 0  # groups added
+        self.nstr = 0  # strings added
+
+    def add(self, model, sym: torch.Tensor, idx, B: int, C: int, H: int, W: int, parity: int) -> None:
+        assert self.groups[self.done] == (B, C, H, W, parity), (self.groups[self.done], (B, C, H, W, parity))
+        from .ops import Workspace
+        lib = L.load()
+        nws = lib.hyres_wrans_workspace_bytes(B, C, H, W, parity)
+        if nws < 0:
+            raise ValueError(f"wrans: bad latent shape B={B} C={C} H={H} W={W} parity={parity}")
+        ws = Workspace.get(int(nws), self.device, "wrans")
+        offs_ptr = self.offs.data_ptr() + 8 * self.nstr
+        L.call("hyres_wrans_encode", sym.data_ptr(), L.ptr(idx), B, C, H, W, parity,
+               *_table_args(_tables_dev(model, self.device)), self.out.data_ptr(), self.out.numel(), offs_ptr,
+               int(self.done > 0), ws.data_ptr(), ws.numel(), L.stream())
+        self.done += 1
+        self.nstr += B
+
+    def finish(self) -> list:
+        assert self.done == len(self.groups)
+        offs = self.offs.cpu().tolist()  # the string lengths: the first copy to the host (waits for the stream)
+        data = self.out[:offs[-1]].cpu().numpy().tobytes()  # the packed bytes: the second and last
+        out, k = [], 0
+        for g in self.groups:
+            out.append([data[offs[k + b]:offs[k + b + 1]] for b in range(g[0])])
+            k += g[0]
+        return out
+
+
+class DeviceDecoder:
+    """The strings of one decompress call: validated on the host (ValueError before anything is launched), copied
+    into one pinned buffer with their offset table and uploaded once; ``decode`` then queues one launch per group."""
+
+    def __init__(self, device, groups, strings):
+        """``groups``: (B, C, H, W, parity) per group; ``strings``: the groups' lists of bytes, in the same order."""
+        self.device = device
+        self.groups = list(groups)
+        flat = []
+        for (B, C, H, W, parity), ss in zip(self.groups, strings):
+            ss = resolve(list(ss))
+            if len(ss) != B:
+                raise ValueError(f"wrans: {len(ss)} strings for a batch of {B}")
+            for s in ss:
+                wrans_validate(bytes(s), C, H, W, parity)
+            flat += ss
+        offs = np.zeros(len(flat) + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in flat], out=offs[1:])
+        nb = int(offs[-1])
+        # one pinned buffer: [offset table | string bytes] (the table is a multiple of 8 bytes, every string of 4)
+        head = 8 * len(offs)
+        host = torch.empty(head + nb, dtype=torch.uint8, pin_memory=True)
+        hv = host.numpy()
+        hv[:head] = offs.view(np.uint8)
+        hv[head:] = np.frombuffer(b"".join(flat), dtype=np.uint8)
+        self.buf = host.to(device, non_blocking=True)  # the one upload of the call
+        self._host = host  # pinned source stays alive until the copy has run
+        self.head = head
+        self.first = np.cumsum([0] + [g[0] for g in self.groups]).tolist()
+
+    def decode(self, k: int, model, idx, params: Node = None, M: int = 0) -> torch.Tensor:
+        """Group k -> the full symbol array [B, C*H*W] (int32, device); no host wait."""
+        B, C, H, W, parity = self.groups[k]
+        sym = torch.empty((B, C * H * W), dtype=torch.int32, device=self.device)
+        L.call("hyres_wrans_decode", self.buf.data_ptr() + self.head, self.buf.data_ptr() + 8 * self.first[k],
+               L.ptr(idx), B, C, H, W, parity, *_table_args(_tables_dev(model, self.device)),
+               None if params is None else params.ptr(), 0 if params is None else params.ld, M, sym.data_ptr(),
+               L.stream())
+        return sym
+
+
+def eb_compress_device(eb, z: Node, enc: DeviceEncoder) -> torch.Tensor:
+    """EntropyBottleneck.compress(z) with the device coder: queues the z strings on ``enc``; returns the symbols."""
+    B, H, W, C = z.B, z.H, z.W, z.C
+    sym = torch.empty(B * C * H * W, dtype=torch.int32, device=z.device)
+    L.call("hyres_eb_symbols", z.ptr(), z.ld, _medians(eb).data_ptr(), B, H, W, C, sym.data_ptr(), None, 0, 0,
+           L.stream())
+    enc.add(eb, sym, None, B, C, H, W, -1)
+    return sym
+
+
+def eb_dequant(eb, sym: torch.Tensor, B: int, H: int, W: int, device) -> Node:
+    C = eb.channels
+    z_hat = Node.new(B, H, W, C, device, rg=False)
+    L.call("hyres_eb_symbols", None, 0, _medians(eb).data_ptr(), B, H, W, C, sym.data_ptr(), z_hat.ptr(), z_hat.ld, 1,
+           L.stream())
+    return z_hat
+
+
+def eb_decompress_device(eb, dec: DeviceDecoder, k: int, H: int, W: int) -> Node:
+    """Group k of ``dec`` -> z_hat (NHWC Node)."""
+    sym = dec.decode(k, eb, None)
+    return eb_dequant(eb, sym, dec.groups[k][0], H, W, dec.device)
+
+
+def gc_compress_device(gc, y: Node, params: Node, M: int, parity: int, enc: DeviceEncoder) -> torch.Tensor:
+    """GaussianConditional.compress of one checkerboard pass with the device coder: only the positions the pass
+    owns are coded. Queues the strings on ``enc``; returns the full symbol array (for hyres_gc_dequant)."""
+    sym, idx = _gc_indexes(gc, params, M, y, parity)
+    enc.add(gc, sym, idx, params.B, M, params.H, params.W, parity)
+    return sym
+
+
+def gc_decompress_device(gc, dec: DeviceDecoder, k: int, params: Node, M: int, out: Node,
+                         accumulate: bool = False) -> Node:
+    """Group k of ``dec`` -> ``out`` (+)= sym + mean; unowned positions get round(-mean) + mean as on the host path."""
+    _, idx = _gc_indexes(gc, params, M)
+    sym = dec.decode(k, gc, idx, params, M)
+    L.call("hyres_gc_dequant", sym.data_ptr(), params.ptr(), params.ld, M, params.B, params.H, params.W, out.ptr(),
+           out.ld, int(accumulate), L.stream())
+    return out

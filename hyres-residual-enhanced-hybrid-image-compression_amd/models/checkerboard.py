@@ -42,9 +42,13 @@ class LightWeightCheckerboard(CompressionModel):
     # the reference does; False (default): dequantise the encoded symbols on the device (identical values)
     decode_in_compress = False
 
-    def __init__(self, N=128, M=192):
+    def __init__(self, N=128, M=192, device_coder: Optional[bool] = None):
+        """``device_coder``: code the strings on the GPU in the wave-interleaved format HRW1 (hyres_hip/entropy_coding.py
+        DeviceEncoder / DeviceDecoder) instead of compressai's format on the host; None takes HYRES_ENTROPY_CODER
+        (host | device, default host). A model on the CPU keeps the host coder either way."""
         super().__init__()
         self.N, self.M = N, M
+        self.device_coder = EC.coder_from_env() if device_coder is None else bool(device_coder)
         self.entropy_bottleneck = EntropyBottleneck(N)
         self.gaussian_conditional = GaussianConditional(None)
         self.quantizer = Quantizer()
@@ -135,6 +139,76 @@ class LightWeightCheckerboard(CompressionModel):
         params_a = self.param_aggregation.hip(None, latent)  # cat([latent, 0]): zero half skipped
         return lc, params_a
 
+    def on_device_coder(self, dev) -> bool:
+        """compress / decompress take the device coder (else the host coder, unchanged)."""
+        return self.device_coder and dev.type == "cuda"
+
+    def _groups(self, B: int, h: int, w: int):
+        """(B, C, H, W, parity) of the z, anchor and non-anchor strings for a z of h x w."""
+        return [(B, self.N, h, w, -1), (B, self.M, 4 * h, 4 * w, 0), (B, self.M, 4 * h, 4 * w, 1)]
+
+    def _compress_device(self, x, dev, start_time):
+        """compress with the device coder: symbols and indexes never leave the GPU; the offset table and the packed
+        bytes of all strings are the only copies to the host. Only the positions a checkerboard pass owns are coded.
+        ``decode_in_compress`` decodes each stage's just-written strings (download, validate, upload, decode)."""
+        M = self.M
+        gc, eb = self.gaussian_conditional, self.entropy_bottleneck
+        xn = O.to_nhwc(x.to(dev).float().contiguous(), rg=False)
+        y = self._g_a(None, xn)
+        z = self.h_a.hip(None, y)
+        B = z.B
+        groups = self._groups(B, z.H, z.W)
+        literal = self.decode_in_compress
+        encs = [EC.DeviceEncoder(dev, [g]) for g in groups] if literal else [EC.DeviceEncoder(dev, groups)] * 3
+        strings = [None, None, None]
+        sym = EC.eb_compress_device(eb, z, encs[0])
+        if literal:
+            strings[0] = encs[0].finish()[0]
+            z_hat = EC.eb_decompress_device(eb, EC.DeviceDecoder(dev, groups[:1], strings[:1]), 0, z.H, z.W)
+        else:
+            z_hat = EC.eb_dequant(eb, sym, B, z.H, z.W, dev)
+        lc, params_a = self._hyper(z_hat, y.H, y.W)
+        sym = EC.gc_compress_device(gc, y, params_a, M, 0, encs[1])
+        ya_hat = Node.new(y.B, y.H, y.W, M, dev, rg=False)
+        if literal:
+            strings[1] = encs[1].finish()[0]
+            EC.gc_decompress_device(gc, EC.DeviceDecoder(dev, groups[1:2], strings[1:2]), 0, params_a, M, ya_hat)
+        else:
+            L.call("hyres_gc_dequant", sym.data_ptr(), params_a.ptr(), params_a.ld, M, y.B, y.H, y.W, ya_hat.ptr(),
+                   ya_hat.ld, 0, L.stream())
+        self.context_prediction.hip(None, ya_hat, out=lc.slice(2 * M, 4 * M))
+        params_na = self.param_aggregation.hip(None, lc)
+        EC.gc_compress_device(gc, y, params_na, M, 1, encs[2])
+        if literal:
+            strings[2] = encs[2].finish()[0]
+        else:
+            strings = encs[0].finish()
+        return {
+            "strings": [[strings[1], strings[2]], strings[0]],
+            "shape": torch.Size([z.H, z.W]),
+            "time": time.time() - start_time,
+        }
+
+    def _decompress_device(self, strings, shape, dev, start_time):
+        """decompress with the device coder: every string is validated on the host (ValueError, nothing launched),
+        all strings go up in one pinned copy, and the three decode launches are queued between the conv launches:
+        no device-to-host copy and no host wait."""
+        M = self.M
+        gc, eb = self.gaussian_conditional, self.entropy_bottleneck
+        h, w = int(shape[0]), int(shape[1])
+        B = len(strings[1])
+        dec = EC.DeviceDecoder(dev, self._groups(B, h, w), [strings[1], strings[0][0], strings[0][1]])
+        z_hat = EC.eb_decompress_device(eb, dec, 0, h, w)
+        H, W = h * 4, w * 4
+        lc, params_a = self._hyper(z_hat, H, W)
+        y_hat = Node.new(B, H, W, M, dev, rg=False)
+        EC.gc_decompress_device(gc, dec, 1, params_a, M, y_hat)
+        self.context_prediction.hip(None, y_hat, out=lc.slice(2 * M, 4 * M))
+        params_na = self.param_aggregation.hip(None, lc)
+        EC.gc_decompress_device(gc, dec, 2, params_na, M, y_hat, accumulate=True)
+        x_hat = O.to_nchw(self._g_s(None, y_hat)).clamp_(0, 1)
+        return {"x_hat": x_hat, "time": time.time() - start_time}
+
     @torch.no_grad()
     def compress(self, x):
         """models/checkerboard.py:167-201: strings [[anchor, non_anchor], z] (one string per image each).
@@ -142,6 +216,8 @@ class LightWeightCheckerboard(CompressionModel):
         trip exactly, so here they are dequantised on the device from the encoded symbols instead."""
         start_time = time.time()
         dev = next(self.parameters()).device
+        if self.on_device_coder(dev):
+            return self._compress_device(x, dev, start_time)
         M = self.M
         gc, eb = self.gaussian_conditional, self.entropy_bottleneck
         xn = O.to_nhwc(x.to(dev).float().contiguous(), rg=False)
@@ -180,6 +256,8 @@ class LightWeightCheckerboard(CompressionModel):
         """models/checkerboard.py:203-240 (including its ``g_s(y_hat).clamp_(0, 1)``)."""
         start_time = time.time()
         dev = next(self.parameters()).device
+        if self.on_device_coder(dev):
+            return self._decompress_device(strings, shape, dev, start_time)
         M = self.M
         gc, eb = self.gaussian_conditional, self.entropy_bottleneck
         h, w = int(shape[0]), int(shape[1])

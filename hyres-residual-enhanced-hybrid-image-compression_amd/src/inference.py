@@ -35,6 +35,9 @@ def parse_args(argv):
     p.add_argument("--cuda", type=lambda x: str(x).lower() == "true", default=True,
                    help="Use cuda if available (default: %(default)s)")
     p.add_argument("--save-components", action="store_true", help="Save JPEG and residual components")
+    p.add_argument("--entropy-coder", choices=("host", "device"), default=None,
+                   help="rANS coder of the residual strings: host (compressai's format) or device (HIP, the "
+                        "wave-interleaved format HRW1); default: HYRES_ENTROPY_CODER, else host")
     return p.parse_args(argv)
 
 
@@ -98,7 +101,8 @@ def main(argv):
     if not ckpt.is_file():
         raise RuntimeError(f'"{ckpt}" is not a valid file.')
     state_dict = load_checkpoint(ckpt)
-    model = ResidualJPEGCompression(base_model=LightWeightCheckerboard(N=args.N, M=args.M),
+    coder = None if args.entropy_coder is None else args.entropy_coder == "device"
+    model = ResidualJPEGCompression(base_model=LightWeightCheckerboard(N=args.N, M=args.M, device_coder=coder),
                                     jpeg_quality=args.jpeg_quality)
     model.load_state_dict(state_dict)
     model = model.to(device).eval()

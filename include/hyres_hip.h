@@ -607,6 +607,47 @@ int hyres_rans_decode_with_indexes(const unsigned char* in, long long in_len, co
                                    int ncdf, int* symbols_out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Device rANS coder (opt-in, HYRES_ENTROPY_CODER=device): the wave-interleaved string format HRW1 (csrc/wrans_core.h,
+ * DESIGN.md). One string per image and pass: "HRW1", n, n_esc, n_words, 64 lane states, the escape values, the payload
+ * words. The coded symbols of a [C,H,W] latent are the positions, in (c, h, w) order, that the checkerboard ``parity``
+ * (0 anchor, 1 non-anchor, -1 all) owns; ``sym`` / ``idx`` are the full [B][C][H][W] arrays of hyres_gc_symbols /
+ * hyres_eb_symbols (idx == NULL: the CDF of position (c, h, w) is row c). CDF tables as for the host coder, on the
+ * device for the device calls. Not compressai's wire format: hyres_rans_* keeps that. */
+/* ------------------------------------------------------------------------------------------ */
+/* coded symbols of one string, or -1 on a bad shape (host) */
+long long hyres_wrans_count(int C, int H, int W, int parity);
+/* the most bytes one string can take: 528 + 8 per coded symbol, or -1 (host) */
+long long hyres_wrans_max_string_bytes(int C, int H, int W, int parity);
+/* workspace of hyres_wrans_encode for B strings, or -1 (host) */
+long long hyres_wrans_workspace_bytes(int B, int C, int H, int W, int parity);
+/* Encodes B strings and packs them one after the other into ``out`` (capacity out_cap >= B * max_string_bytes behind
+ * the start offset; a write past it is dropped). offs[0..B] (device) receives the byte offsets: offs[b + 1] - offs[b]
+ * is string b's length. chain = 0 starts at offs[0] = 0; chain = 1 starts at the offs[0] an earlier call on the
+ * stream left there, so several calls fill one buffer and one offset table (pass offs + B of the previous call).
+ * Two kernels on ``s``, no host sync. */
+int hyres_wrans_encode(const int* sym, const int* idx, int B, int C, int H, int W, int parity, const int* cdfs,
+                       int cdf_stride, const int* cdf_sizes, const int* offsets, int ncdf, unsigned char* out,
+                       long long out_cap, long long* offs, int chain, void* ws, long long ws_bytes,
+                       hyres_stream_t s);
+/* Decodes string b at strings + offs[b] (4-byte aligned, offs[0..B] on the device; validate every string with
+ * hyres_wrans_validate on the host first) into the full symbol array sym_out [B][C][H][W]: owned positions from the
+ * stream, the others (int)rintf(0.f - mean) with mean = params[pixel * ldp + M + c] (NHWC params [.., scales | means];
+ * params may be NULL for parity -1). Reads are clamped to each string's end and to the tables. One kernel on ``s``. */
+int hyres_wrans_decode(const unsigned char* strings, const long long* offs, const int* idx, int B, int C, int H, int W,
+                       int parity, const int* cdfs, int cdf_stride, const int* cdf_sizes, const int* offsets, int ncdf,
+                       const float* params, int ldp, int M, int* sym_out, hyres_stream_t s);
+/* one string holds the coded symbols of a [C,H,W] latent under ``parity``: magic, n, lengths consistent with the byte
+ * count; HYRES_E_ARG with the reason otherwise (host) */
+int hyres_wrans_validate(const unsigned char* in, long long in_len, int C, int H, int W, int parity);
+/* the same coder on host memory, one string (csrc/wrans_core.h); out == NULL: *out_len only. No GPU call (host) */
+int hyres_wrans_encode_host(const int* sym, const int* idx, int C, int H, int W, int parity, const int* cdfs,
+                            int cdf_stride, const int* cdf_sizes, const int* offsets, int ncdf, unsigned char* out,
+                            long long out_cap, long long* out_len);
+int hyres_wrans_decode_host(const unsigned char* in, long long in_len, const int* idx, int C, int H, int W, int parity,
+                            const int* cdfs, int cdf_stride, const int* cdf_sizes, const int* offsets, int ncdf,
+                            const float* params, int ldp, int M, int* sym_out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* JPEG 4:2:2 base layer: bit-exact with libjpeg-turbo at PyTurboJPEG's defaults */
 /* ------------------------------------------------------------------------------------------ */
 /* libjpeg's quality-scaled baseline quantisation tables (entries 1..255) in zigzag order, i.e. the two DQT
