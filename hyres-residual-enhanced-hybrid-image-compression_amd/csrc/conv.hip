@@ -12,7 +12,10 @@
 //     is permuted so that lane-half h consumes k = 16h + s at MFMA step s: one ds_read_b128 feeds four
 //     consecutive MFMA steps (conflict-free with the 36-float row pitch).
 // Weight gradients use a second kernel (P^T Q over pixels, split-K slabs + deterministic reduce).
-#include "conv_common.h"
+// The halo-tiled 3x3 kernels (conv3x3_halo_f16_kernel, conv3x3_wres_{f16,f32,bf6}_kernel) share their tile geometry,
+// tile walk, halo address, f16 halo staging, fused-operand epilogue and weight-slice decode with ru_fused.hip
+// through halo_common.h.
+#include "halo_common.h"
 #include <limits>
 
 namespace hyres {
@@ -40,15 +43,7 @@ struct ConvArgs {
                  // hyres_conv_tuning key 19, default 1) instead of 80-B padded rows
 };
 
-// Buffer resource of an epilogue operand: an absent operand (p == NULL) gets an empty resource, so its loads return
-// 0 without a branch (a load behind a branch is waited on at the join: the epilogue's loads would serialise)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t opnd_rsrc(const void* p, long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, p ? (int)std::min<long long>(bytes, 0x7FFFFFF0LL) : 0,
-                                             0x00020000);
-}
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
+// opnd_rsrc, bload4 (buffer resources of the epilogue operands), st4: conv_common.h
 __device__ __forceinline__ half4_t bload4h(__amdgpu_buffer_rsrc_t r, int off) {
     return __builtin_bit_cast(half4_t, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
 }
@@ -135,8 +130,6 @@ __device__ __forceinline__ void epi_store(const hyres_epilogue& e, float* y, int
         *yp = v;
     }
 }
-
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // float4 variant of epi_store for channels n..n+3 (all operands 16B aligned).
 template <bool H = false, bool SAB = false>
@@ -277,9 +270,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvArgs& a) {
     // the N tiles sharing an A tile then hit one L2 instead of being spread over all eight.
     int m0, n0;
     if (a.xcd) {
-        const int nb = gridDim.x, hw = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, x = hw & 7;
-        const int l = x * q + min(x, r) + (hw >> 3);
+        const int l = xcd_logical_block();
         const int ntn = (g.Co + BN - 1) / BN;
         m0 = (l / ntn) * BM;
         n0 = (l - (l / ntn) * ntn) * BN;
@@ -801,10 +792,8 @@ void conv_fwd_h_kernel(const ConvArgs a) {
 // registers) come straight from L2 in MFMA layout, one tap ahead.  L2->CU bytes per output pixel drop from
 // ~3.4 KB to ~1.5 KB.  Taps: any 9 offsets within [-1, 1]^2 (the conv and its input-gradient), stride 1,
 // same-size output, Ci % 32 == 0, Co % 64 == 0, Wo % 64 == 0.  IO: bit 0 X fp16, bit 1 Y/res/aux fp16.
-constexpr int HALO_R = 4, HALO_TW = 64, HALO_HR = HALO_R + 2, HALO_HW = HALO_TW + 2;
-constexpr int HALO_NPX = HALO_HR * HALO_HW;  // 396 halo pixels
-constexpr int HALO_PH = 40;                   // halves per staged pixel (32 channels + 8 pad: 80-B pitch)
-constexpr int HALO_E = HALO_NPX * 8;          // float4 elements of one 32-channel halo chunk
+// Tile geometry (HALO_R, HALO_TW, HALO_PH, halo_hw / halo_npx / halo_elems of the radius): halo_common.h
+constexpr int HALO_E = halo_elems(1, 8);      // float4 elements of one 32-channel halo chunk (396 px x 8)
 constexpr int HALO_PE = (HALO_E + 2) / 3;     // per staging part (3 parts per chunk)
 constexpr int HALO_PV = (HALO_PE + 255) / 256;
 
@@ -812,7 +801,7 @@ template <int IO>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const ConvArgs a) {
     constexpr bool XH = (IO & 1) != 0, YH = (IO & 2) != 0;
     constexpr int XES = XH ? 2 : 4;
-    constexpr int HBUF = HALO_NPX * HALO_PH;  // halves per buffer
+    constexpr int HBUF = halo_npx(1) * HALO_PH;  // halves per buffer
     constexpr int CP = 64 + 4;                // epilogue staging pitch (floats)
     static_assert(2 * 64 * CP * 4 <= 2 * HBUF * 2, "epilogue staging fits in the halo buffers");
     __shared__ __attribute__((aligned(16))) _Float16 hal[2 * HBUF];
@@ -824,12 +813,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const ConvArgs
     // tile decode, XCD-aware (conv_fwd_body): N tiles fastest, then row tiles (vertical neighbours share
     // two of the six halo rows through one L2), column tiles, images
     const int nnt = g.Co / 64, nrt = (g.Ho + HALO_R - 1) / HALO_R, nct = g.Wo / HALO_TW;
-    int l;
-    {
-        const int nb = gridDim.x, hw = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, x = hw & 7;
-        l = x * q + min(x, r) + (hw >> 3);
-    }
+    int l = xcd_logical_block();
     const int nt = l % nnt; l /= nnt;
     const int rt = l % nrt; l /= nrt;
     const int ct = l % nct;
@@ -850,37 +834,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const ConvArgs
     const int lr = lane & 31, lh = lane >> 5;
 
     // ---- halo staging (part p of chunk c: elements [p*PE, (p+1)*PE) of the 396 px x 8 float4)
-    std::conditional_t<XH, half4_t, float4> hreg[HALO_PV];  // fp16 X: raw halves until the LDS store
+    HaloReg<XH> hreg[HALO_PV];  // fp16 X: raw halves until the LDS store
     auto hload = [&](int part, int c) {
-        const int ci0 = c * 32;
-#pragma unroll
-        for (int q = 0; q < HALO_PV; ++q) {
-            const int e = part * HALO_PE + tid + 256 * q;
-            const int px = e >> 3, c4 = e & 7;
-            const int hr = px / HALO_HW, hc = px - hr * HALO_HW;
-            const int ih = i0 - 1 + hr, iw = j0 - 1 + hc;
-            const bool ok = e < (part + 1) * HALO_PE && e < HALO_E && (unsigned)ih < (unsigned)g.Hi &&
-                            (unsigned)iw < (unsigned)g.Wi;
-            const int off = ok ? ((ih * g.Wi + iw) * g.ldx + ci0 + 4 * c4) * XES : (int)0x80000000;
-            if constexpr (XH) {
-                hreg[q] = __builtin_bit_cast(half4_t, __builtin_amdgcn_raw_buffer_load_b64(xr, off, 0, 0));
-            } else {
-                hreg[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
-            }
-        }
+        halo16_load<XH, 256>(hreg, xr, part * HALO_PE + tid, min((part + 1) * HALO_PE, HALO_E), i0, j0, g.Hi, g.Wi,
+                             g.ldx, c * 32);
     };
     auto hstore = [&](int part, int buf) {
-#pragma unroll
-        for (int q = 0; q < HALO_PV; ++q) {
-            const int e = part * HALO_PE + tid + 256 * q;
-            if (e < (part + 1) * HALO_PE && e < HALO_E) {
-                const int px = e >> 3, c4 = e & 7;
-                half4_t h;
-                if constexpr (XH) h = hreg[q];
-                else h = half4_t{(_Float16)hreg[q].x, (_Float16)hreg[q].y, (_Float16)hreg[q].z, (_Float16)hreg[q].w};
-                *reinterpret_cast<half4_t*>(&hal[buf * HBUF + px * HALO_PH + 4 * c4]) = h;
-            }
-        }
+        halo16_store<XH, 256>(hal + buf * HBUF, hreg, part * HALO_PE + tid, min((part + 1) * HALO_PE, HALO_E));
     };
     // ---- B fragments of one tap (both 16-deep k-steps of the chunk): W2[co][t][ci], fp32 -> fp16
     const int co = n0 + wn * 32 + lr;
@@ -928,7 +888,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const ConvArgs
 #pragma unroll
                 for (int at = 0; at < 4; ++at) {
                     const int orow = 2 * wm + (at >> 1);  // output row within the tile
-                    const int px = (orow + 1 + o.x) * HALO_HW + (at & 1) * 32 + lr + 1 + o.y;
+                    const int px = (orow + 1 + o.x) * halo_hw(1) + (at & 1) * 32 + lr + 1 + o.y;
                     const half8 af = *reinterpret_cast<const half8*>(&H[px * HALO_PH + 16 * ks + 8 * lh]);
                     acc[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf[ks], acc[at], 0, 0, 0);
                 }
@@ -978,16 +938,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const ConvArgs
 // epilogue is applied from the accumulators directly (per-lane scalar epi_store: the LDS is full).
 // 8 waves = 4 output rows x 2 co halves, 2 A tiles (64 px) each; tiles are walked XCD-contiguously.
 constexpr int WRES_LDS_B = 2 * 9 * 64 * HALO_PH;  // halves: [chunk][tap][co][40]
-constexpr int WRES_HV = (HALO_E + 511) / 512;     // halo float4 per thread per chunk (7)
+constexpr int WRES_HV = halo_per_thread(1, 8, 512);  // halo float4 per thread per chunk (7)
 
 template <int IO>
 __global__ __launch_bounds__(512, 2) void conv3x3_wres_f16_kernel(const ConvArgs a, int ntiles, int groups) {
     constexpr bool XH = (IO & 1) != 0, YH = (IO & 2) != 0;
     constexpr int XES = XH ? 2 : 4;
-    constexpr int HBUF = HALO_NPX * HALO_PH;
+    constexpr int HBUF = halo_npx(1) * HALO_PH;
     __shared__ __attribute__((aligned(16))) _Float16 lds[WRES_LDS_B + 2 * HBUF];
     __shared__ int2 tapoff[9];
-    typedef _Float16 half8 __attribute__((ext_vector_type(8)));
     _Float16* const Bs = lds;
     _Float16* const Hs = lds + WRES_LDS_B;
     // whole VGPR file (as conv3x3_wres_bf6_kernel, DESIGN §4 "Cross-kernel interference"): IO 1 allocated 248 and left
@@ -1004,15 +963,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wres_f16_kernel(const ConvArgs
     const int nb = gridDim.x / groups;  // blocks per channel group
     const int grp = blockIdx.x / nb, bg = blockIdx.x - grp * nb;
     const int n0 = grp * 64;
-    const int xcd = bg & 7, nx = (nb + 7 - xcd) >> 3, jx = bg >> 3;  // blocks of this XCD, index among them
-    const int q = ntiles >> 3, rr8 = ntiles & 7;
-    const int tbeg = xcd * q + min(xcd, rr8), tcnt = q + (xcd < rr8 ? 1 : 0);
-    const int mytiles = jx < tcnt ? (tcnt - 1 - jx) / nx + 1 : 0;
+    const HaloWalk walk = halo_walk(bg, nb, ntiles, nrt, nct);
     if (tid < 9) tapoff[tid] = make_int2(g.dh[tid], g.dw[tid]);
 
     // ---- the 64-channel weight slice, fp32 W2[co][t][ci] -> fp16 Bs[(c*9 + t)*64 + co][k] (ci = 32c + k)
     for (int f = tid; f < 64 * 9 * 16; f += 512) {
-        const int co = f / 144, rem = f - co * 144, t = rem >> 4, ci = 4 * (rem & 15);
+        const auto [co, t, ci] = wres_weight_index(f);
         const float4 w = ld4(a.w2 + (long long)(n0 + co) * a.ldw + t * 64 + ci);
         const half4_t h = {(_Float16)w.x, (_Float16)w.y, (_Float16)w.z, (_Float16)w.w};
         *reinterpret_cast<half4_t*>(&Bs[(((ci >> 5) * 9 + t) * 64 + co) * HALO_PH + (ci & 31)]) = h;
@@ -1025,30 +981,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wres_f16_kernel(const ConvArgs
     const int orow = wave & 3, wn = wave >> 2;
     const int lr = lane & 31, lh = lane >> 5;
 
-    auto tile_of = [&](int k, int& b, int& i0, int& j0) {
-        int l = tbeg + jx + k * nx;
-        const int rt = l % nrt; l /= nrt;
-        const int ct = l % nct;
-        b = l / nct;
-        i0 = rt * HALO_R;
-        j0 = ct * HALO_TW;
-    };
     // halo chunks are prefetched TWO steps ahead (two register sets, alternating): one step of MFMA work
     // (~2.3k cycles per SIMD) does not cover an HBM-bound 50 KB-per-CU chunk load
-    using HRT = std::conditional_t<XH, half4_t, float4>;  // fp16 X: raw halves until the LDS store
+    using HRT = HaloReg<XH>;  // fp16 X: raw halves until the LDS store
     auto hload = [&](HRT (&h)[WRES_HV], int step) {
-        int b, i0, j0;
-        tile_of(step >> 1, b, i0, j0);
+        const HaloTile tl = walk.tile(step >> 1);
         const int c = step & 1;
-        const int base = b * (int)img;  // element offset of image b (host checks the batch < 2 GB)
+        const int base = tl.b * (int)img;  // element offset of image b (host checks the batch < 2 GB)
+        // its own load / store loops, not halo16_load / halo16_store: through those IO 2 spilled (12 B of scratch)
 #pragma unroll
         for (int v = 0; v < WRES_HV; ++v) {
-            const int e = tid + 512 * v;
-            const int px = e >> 3, c4 = e & 7;
-            const int hr = px / HALO_HW, hc = px - hr * HALO_HW;
-            const int ih = i0 - 1 + hr, iw = j0 - 1 + hc;
-            const bool ok = e < HALO_E && (unsigned)ih < (unsigned)g.Hi && (unsigned)iw < (unsigned)g.Wi;
-            const int off = ok ? (base + (ih * g.Wi + iw) * g.ldx + 32 * c + 4 * c4) * XES : (int)0x80000000;
+            const int off = halo_offset<1, 8>(tid + 512 * v, tl.i0, tl.j0, g.Hi, g.Wi, g.ldx, base + 32 * c, XES);
             if constexpr (XH) {
                 h[v] = __builtin_bit_cast(half4_t, __builtin_amdgcn_raw_buffer_load_b64(xr, off, 0, 0));
             } else {
@@ -1080,12 +1023,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wres_f16_kernel(const ConvArgs
     const float slope = (a.e.act == HYRES_ACT_PRELU) ? a.e.slope[0] : 0.f;
     const bool pre_res = a.e.kind == HYRES_EPI_BIAS && a.e.res != nullptr;
     float4 rres[2][4];  // the tile's residual operand, prefetched one step before the epilogue
-    const int steps = mytiles * 2;  // two 32-channel chunks per tile
+    const int steps = walk.mytiles * 2;  // two 32-channel chunks per tile
     auto tile_pix = [&](int k, int at, int& i, long long& pix) {
-        int b, i0, j0;
-        tile_of(k, b, i0, j0);
-        i = i0 + orow;
-        pix = ((long long)b * g.Ho + i) * g.Wo + j0 + 32 * at + lr;
+        const HaloTile tl = walk.tile(k);
+        i = tl.i0 + orow;
+        pix = ((long long)tl.b * g.Ho + i) * g.Wo + tl.j0 + 32 * at + lr;
     };
     auto body = [&](int s, HRT (&hl)[WRES_HV], const HRT (&hs)[WRES_HV]) {
         const int k = s >> 1, c = s & 1;
@@ -1112,11 +1054,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wres_f16_kernel(const ConvArgs
             const int2 o = tapoff[t];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const half8 bf = *reinterpret_cast<const half8*>(&Bc[(t * 64 + wn * 32 + lr) * HALO_PH + 16 * ks + 8 * lh]);
+                const halfx8_t bf = *reinterpret_cast<const halfx8_t*>(&Bc[(t * 64 + wn * 32 + lr) * HALO_PH + 16 * ks + 8 * lh]);
 #pragma unroll
                 for (int at = 0; at < 2; ++at) {
-                    const int px = (orow + 1 + o.x) * HALO_HW + at * 32 + lr + 1 + o.y;
-                    const half8 af = *reinterpret_cast<const half8*>(&H[px * HALO_PH + 16 * ks + 8 * lh]);
+                    const int px = (orow + 1 + o.x) * halo_hw(1) + at * 32 + lr + 1 + o.y;
+                    const halfx8_t af = *reinterpret_cast<const halfx8_t*>(&H[px * HALO_PH + 16 * ks + 8 * lh]);
                     acc[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, af, acc[at], 0, 0, 0);
                 }
             }
@@ -1172,7 +1114,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wres_f16_kernel(const ConvArgs
 // the implicit-GEMM kernel up to the K order.
 constexpr int WF_PK = 36;  // floats per staged row (32 + 4 pad)
 constexpr int WF_LDS_W = 2 * 9 * 32 * WF_PK;
-constexpr int WF_LDS_H = HALO_NPX * WF_PK;
+constexpr int WF_LDS_H = halo_npx(1) * WF_PK;
 
 // Epilogue (BIAS kind: bias, residual, pre-activation store, ReLU / PReLU / ReLU-mask, accumulate): every operand
 // it reads (bias, residual, mask, old y) is requested at the START of the tile's second chunk through buffer
@@ -1196,14 +1138,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_f32_kernel(const ConvArgs
     const int nb = gridDim.x / groups;  // group-major, nb % 8 == 0: see conv3x3_wres_f16_kernel
     const int grp = blockIdx.x / nb, bg = blockIdx.x - grp * nb;
     const int n0 = grp * 32;
-    const int xcd = bg & 7, nx = (nb + 7 - xcd) >> 3, jx = bg >> 3;
-    const int q = ntiles >> 3, rr8 = ntiles & 7;
-    const int tbeg = xcd * q + min(xcd, rr8), tcnt = q + (xcd < rr8 ? 1 : 0);
-    const int mytiles = jx < tcnt ? (tcnt - 1 - jx) / nx + 1 : 0;
+    const HaloWalk walk = halo_walk(bg, nb, ntiles, nrt, nct);
     if (tid < 9) tapoff[tid] = make_int2(g.dh[tid], g.dw[tid]);
     // weights W2[co][t][ci] -> Ws[((c*9 + t)*32 + co)*36 + k], ci = 32c + k
     for (int f = tid; f < 32 * 9 * 16; f += 512) {
-        const int co = f / 144, rem = f - co * 144, t = rem >> 4, ci = 4 * (rem & 15);
+        const auto [co, t, ci] = wres_weight_index(f);
         *reinterpret_cast<float4*>(&Ws[(((ci >> 5) * 9 + t) * 32 + co) * WF_PK + (ci & 31)]) =
             ld4(a.w2 + (long long)(n0 + co) * a.ldw + t * 64 + ci);
     }
@@ -1214,30 +1153,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_f32_kernel(const ConvArgs
     const int orow = wave & 3, ph = wave >> 2;  // output row in the tile, 32-pixel half
     const int lr = lane & 31, lh = lane >> 5;
 
-    auto tile_of = [&](int k, int& b, int& i0, int& j0) {
-        int l = tbeg + jx + k * nx;
-        const int rt = l % nrt; l /= nrt;
-        const int ct = l % nct;
-        b = l / nct;
-        i0 = rt * HALO_R;
-        j0 = ct * HALO_TW;
-    };
     float4 hreg[WRES_HV];
     auto hload = [&](int step) {
-        int b, i0, j0;
-        tile_of(step >> 1, b, i0, j0);
+        const HaloTile tl = walk.tile(step >> 1);
         const int c = step & 1;
-        const int base = b * (int)img;
+        const int base = tl.b * (int)img;
 #pragma unroll
-        for (int v = 0; v < WRES_HV; ++v) {
-            const int e = tid + 512 * v;
-            const int px = e >> 3, c4 = e & 7;
-            const int hr = px / HALO_HW, hc = px - hr * HALO_HW;
-            const int ih = i0 - 1 + hr, iw = j0 - 1 + hc;
-            const bool ok = e < HALO_E && (unsigned)ih < (unsigned)g.Hi && (unsigned)iw < (unsigned)g.Wi;
-            const int off = ok ? (base + (ih * g.Wi + iw) * g.ldx + 32 * c + 4 * c4) * 4 : (int)0x80000000;
-            hreg[v] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
-        }
+        for (int v = 0; v < WRES_HV; ++v)
+            hreg[v] = bload4(xr, halo_offset<1, 8>(tid + 512 * v, tl.i0, tl.j0, g.Hi, g.Wi, g.ldx, base + 32 * c, 4));
     };
     auto hstore = [&]() {
 #pragma unroll
@@ -1250,14 +1173,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_f32_kernel(const ConvArgs
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const hyres_epilogue& e = a.e;
-    const float slope = (e.act == HYRES_ACT_PRELU) ? e.slope[0] : 0.f;
-    const long long npix = (long long)g.B * g.Ho * g.Wo;
-    const __amdgpu_buffer_rsrc_t r_bias = opnd_rsrc(e.bias, (long long)g.Co * 4);
-    const __amdgpu_buffer_rsrc_t r_res = opnd_rsrc(e.res, npix * e.ldres * 4);
-    const __amdgpu_buffer_rsrc_t r_mask = opnd_rsrc(e.act == HYRES_ACT_RELU_MASK ? e.aux0 : nullptr, npix * e.ld0 * 4);
-    const __amdgpu_buffer_rsrc_t r_old = opnd_rsrc(e.accumulate ? a.y : nullptr, npix * g.ldy * 4);
-    float4 ebias[4], eres[4], emask[4], eold[4];
-    const int steps = mytiles * 2;
+    WresEpi<false> epi(e, g, a.y);  // no PReLU mask: routing gives that activation to the bf16x6 kernel only
+    const int steps = walk.mytiles * 2;
     if (steps > 0) {
         hload(0);
         hstore();
@@ -1265,31 +1182,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_f32_kernel(const ConvArgs
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
         const int k = s >> 1, c = s & 1;
-        int b, i0, j0;
-        tile_of(k, b, i0, j0);
-        const int i = i0 + orow;
-        const long long pix = ((long long)b * g.Ho + i) * g.Wo + j0 + 32 * ph + lr;
-        if (c == 1) {  // the epilogue's operands, issued before the next halo (vmcnt retires in issue order)
-            const bool okr = i < g.Ho;
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int n = n0 + 8 * qd + 4 * lh;
-                const int ob = n * 4;
-                const int orr = okr ? (int)((pix * e.ldres + n) * 4) : (int)0x80000000;
-                const int om = okr ? (int)((pix * e.ld0 + n) * 4) : (int)0x80000000;
-                const int oy = okr ? (int)((pix * g.ldy + n) * 4) : (int)0x80000000;
-                ebias[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_bias, ob, 0, 0));
-                eres[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_res, orr, 0, 0));
-                emask[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_mask, om, 0, 0));
-                eold[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_old, oy, 0, 0));
-            }
-        }
+        const HaloTile tl = walk.tile(k);
+        const int i = tl.i0 + orow;
+        const long long pix = ((long long)tl.b * g.Ho + i) * g.Wo + tl.j0 + 32 * ph + lr;
+        // the epilogue's operands, issued before the next halo (vmcnt retires in issue order)
+        if (c == 1) epi.request(e, g.ldy, pix, i < g.Ho, n0, lh);
         if (s + 1 < steps) hload(s + 1);
         const float* Wc = Ws + c * 9 * 32 * WF_PK;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int2 o = tapoff[t];
-            const float* arow = &Hs[((orow + 1 + o.x) * HALO_HW + 32 * ph + lr + 1 + o.y) * WF_PK + lh * 16];
+            const float* arow = &Hs[((orow + 1 + o.x) * halo_hw(1) + 32 * ph + lr + 1 + o.y) * WF_PK + lh * 16];
             const float* brow = &Wc[(t * 32 + lr) * WF_PK + lh * 16];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1302,29 +1205,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_f32_kernel(const ConvArgs
             }
         }
         if (c == 1) {
-            if (i < g.Ho) {
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    const int n = n0 + 8 * qd + 4 * lh;
-                    float o[4] = {acc[4 * qd] + ebias[qd].x + eres[qd].x, acc[4 * qd + 1] + ebias[qd].y + eres[qd].y,
-                                  acc[4 * qd + 2] + ebias[qd].z + eres[qd].z, acc[4 * qd + 3] + ebias[qd].w + eres[qd].w};
-                    if (e.out2) st4(e.out2 + pix * e.ldo2 + n, make_float4(o[0], o[1], o[2], o[3]));
-                    if (e.act == HYRES_ACT_RELU) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
-                    } else if (e.act == HYRES_ACT_PRELU) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = o[k] >= 0.f ? o[k] : slope * o[k];
-                    } else if (e.act == HYRES_ACT_RELU_MASK) {
-                        o[0] = emask[qd].x > 0.f ? o[0] : 0.f;
-                        o[1] = emask[qd].y > 0.f ? o[1] : 0.f;
-                        o[2] = emask[qd].z > 0.f ? o[2] : 0.f;
-                        o[3] = emask[qd].w > 0.f ? o[3] : 0.f;
-                    }
-                    st4(a.y + pix * g.ldy + n,
-                        make_float4(o[0] + eold[qd].x, o[1] + eold[qd].y, o[2] + eold[qd].z, o[3] + eold[qd].w));
-                }
-            }
+            epi.apply(acc, e, a.y, g.ldy, pix, i < g.Ho, n0, lh);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         }
@@ -1348,9 +1229,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_f32_kernel(const ConvArgs
 // images swizzle the 16-B half of a 32-B row by bit 3 of the row: every ds_read_b128 lane group then hits 16
 // distinct 16-B slots (conflict-free). Same tiles, waves, tile order and epilogue as conv3x3_wres_f32_kernel.
 constexpr int BF6_WPL = 4 * 9 * 32 * 16;  // bf16 per weight plane
-constexpr int BF6_HPL = HALO_NPX * 16;    // bf16 per halo plane
-constexpr int BF6_HE = HALO_NPX * 4;      // float4 per 16-channel halo chunk
-constexpr int BF6_HV = (BF6_HE + 511) / 512;
 // 16-B segment (0 / 1) of element k (0..15) of row r in a swizzled [row][16] bf16 image, as an element offset
 __device__ __forceinline__ int bf6_off(int r, int k) { return r * 16 + ((((k >> 3) ^ (r >> 3)) & 1) << 3) + (k & 7); }
 
@@ -1362,8 +1240,9 @@ __device__ __forceinline__ int bf6_off(int r, int k) { return r * 16 + ((((k >> 
 // enhancement.py:44-51): (4 + 2D) x (64 + 2D) halo pixels; at D = 2 the three halo planes are 52 KB, 159 KB of LDS in all
 template <bool GUARD, int V, int D = 1>
 __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs a, int ntiles, int groups) {
-    constexpr int HW = HALO_TW + 2 * D, NPX = (HALO_R + 2 * D) * HW;  // halo row length, pixels
-    constexpr int HPL = NPX * 16, HE = NPX * 4, HV = (HE + 511) / 512;  // bf16 per halo plane, float4 per chunk
+    constexpr int HW = halo_hw(D);  // halo row length
+    // bf16 per halo plane, float4 per 16-channel chunk and per thread
+    constexpr int HPL = halo_npx(D) * 16, HE = halo_elems(D, 4), HV = halo_per_thread(D, 4, 512);
     __shared__ __attribute__((aligned(16))) __bf16 lds[3 * BF6_WPL + 3 * HPL];
     __shared__ int2 tapoff[9];
     __bf16* const Ws = lds;
@@ -1381,21 +1260,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
     const int nb = gridDim.x / groups;  // group-major, nb % 8 == 0: see conv3x3_wres_f16_kernel
     const int grp = blockIdx.x / nb, bg = blockIdx.x - grp * nb;
     const int n0 = grp * 32;
-    const int xcd = bg & 7, nx = (nb + 7 - xcd) >> 3, jx = bg >> 3;
-    const int q = ntiles >> 3, rr8 = ntiles & 7;
-    const int tbeg = xcd * q + min(xcd, rr8), tcnt = q + (xcd < rr8 ? 1 : 0);
-    const int mytiles = jx < tcnt ? (tcnt - 1 - jx) / nx + 1 : 0;
+    const HaloWalk walk = halo_walk(bg, nb, ntiles, nrt, nct);
     if (tid < 9) tapoff[tid] = make_int2(g.dh[tid], g.dw[tid]);
     // weights W2[co][t][ci] (fp32) -> three bf16 planes, row (chunk c = ci / 16, tap t, co), element ci % 16
     for (int f = tid; f < 32 * 9 * 16; f += 512) {
-        const int co = f / 144, rem = f - co * 144, t = rem >> 4, ci = 4 * (rem & 15);
-        bf16x4_t h, m, l;
-        bf6_split4(ld4(a.w2 + (long long)(n0 + co) * a.ldw + t * 64 + ci), h, m, l);
+        const auto [co, t, ci] = wres_weight_index(f);
         const int row = ((ci >> 4) * 9 + t) * 32 + co;
-        const int o = bf6_off(row, ci & 15);
-        *reinterpret_cast<bf16x4_t*>(&Ws[o]) = h;
-        *reinterpret_cast<bf16x4_t*>(&Ws[BF6_WPL + o]) = m;
-        *reinterpret_cast<bf16x4_t*>(&Ws[2 * BF6_WPL + o]) = l;
+        bf6_put3<BF6_WPL>(Ws, bf6_off(row, ci & 15), ld4(a.w2 + (long long)(n0 + co) * a.ldw + t * 64 + ci));
     }
     const long long img = (long long)g.Hi * g.Wi * g.ldx;
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
@@ -1404,31 +1275,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
     const int orow = wave & 3, ph = wave >> 2;  // output row in the tile, 32-pixel half
     const int lr = lane & 31, lh = lane >> 5;
 
-    auto tile_of = [&](int k, int& b, int& i0, int& j0) {
-        int l = tbeg + jx + k * nx;
-        const int rt = l % nrt; l /= nrt;
-        const int ct = l % nct;
-        b = l / nct;
-        i0 = rt * HALO_R;
-        j0 = ct * HALO_TW;
-    };
     // halo chunks are prefetched TWO steps ahead (two register sets, alternating, as conv3x3_wres_f16_kernel): one
     // 16-channel step is 54 MFMAs per wave (~1.7k cycles), too short to cover an HBM load issued one step ahead
     auto hload = [&](float4 (&hreg)[HV], int step) {  // step = 4 * tile + chunk (16 channels)
-        int b, i0, j0;
-        tile_of(step >> 2, b, i0, j0);
+        const HaloTile tl = walk.tile(step >> 2);
         const int c = step & 3;
-        const int base = b * (int)img;
+        const int base = tl.b * (int)img;
 #pragma unroll
-        for (int v = 0; v < HV; ++v) {
-            const int e = tid + 512 * v;
-            const int px = e >> 2, c4 = e & 3;
-            const int hr = px / HW, hc = px - hr * HW;
-            const int ih = i0 - D + hr, iw = j0 - D + hc;
-            const bool ok = e < HE && (unsigned)ih < (unsigned)g.Hi && (unsigned)iw < (unsigned)g.Wi;
-            const int off = ok ? (base + (ih * g.Wi + iw) * g.ldx + 16 * c + 4 * c4) * 4 : (int)0x80000000;
-            hreg[v] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
-        }
+        for (int v = 0; v < HV; ++v)
+            hreg[v] = bload4(xr, halo_offset<D, 4>(tid + 512 * v, tl.i0, tl.j0, g.Hi, g.Wi, g.ldx, base + 16 * c, 4));
     };
     // the next step's halo is split into its bf16 pieces in registers DURING this step's MFMAs (hsplit, independent
     // VALU work the scheduler interleaves with them); between the two barriers only the LDS stores remain (hput)
@@ -1453,16 +1308,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const hyres_epilogue& e = a.e;
-    const float slope = (e.act == HYRES_ACT_PRELU || e.act == HYRES_ACT_PRELU_MASK) ? e.slope[0] : 0.f;
-    const long long npix = (long long)g.B * g.Ho * g.Wo;
-    const __amdgpu_buffer_rsrc_t r_bias = opnd_rsrc(e.bias, (long long)g.Co * 4);
-    const __amdgpu_buffer_rsrc_t r_res = opnd_rsrc(e.res, npix * e.ldres * 4);
-    const __amdgpu_buffer_rsrc_t r_mask = opnd_rsrc(
-        (e.act == HYRES_ACT_RELU_MASK || e.act == HYRES_ACT_PRELU_MASK) ? e.aux0 : nullptr, npix * e.ld0 * 4);
-    const __amdgpu_buffer_rsrc_t r_old = opnd_rsrc(e.accumulate ? a.y : nullptr, npix * g.ldy * 4);
-    float4 ebias[4], eres[4], emask[4], eold[4];
-    float pslope = 0.f;  // HYRES_ACT_PRELU_MASK: this thread's share of sum_{pre <= 0} pre * gradient
-    const int steps = mytiles * 4;
+    WresEpi<true> epi(e, g, a.y);
+    const int steps = walk.mytiles * 4;
     float4 hA[HV], hB[HV];
     if (steps > 0) {
         hload(hA, 0);
@@ -1474,25 +1321,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
     // step s: the set that held step s's halo (stored) receives step s + 2; the other holds step s + 1
     auto body = [&](int s, float4 (&hl)[HV], const float4 (&hs)[HV]) {
         const int k = s >> 2, c = s & 3;
-        int b, i0, j0;
-        tile_of(k, b, i0, j0);
-        const int i = i0 + orow;
-        const long long pix = ((long long)b * g.Ho + i) * g.Wo + j0 + 32 * ph + lr;
-        if (c == 3) {  // the epilogue's operands, issued before the next halo (vmcnt retires in issue order)
-            const bool okr = i < g.Ho;
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int n = n0 + 8 * qd + 4 * lh;
-                const int ob = n * 4;
-                const int orr = okr ? (int)((pix * e.ldres + n) * 4) : (int)0x80000000;
-                const int om = okr ? (int)((pix * e.ld0 + n) * 4) : (int)0x80000000;
-                const int oy = okr ? (int)((pix * g.ldy + n) * 4) : (int)0x80000000;
-                ebias[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_bias, ob, 0, 0));
-                eres[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_res, orr, 0, 0));
-                emask[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_mask, om, 0, 0));
-                eold[qd] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_old, oy, 0, 0));
-            }
-        }
+        const HaloTile tl = walk.tile(k);
+        const int i = tl.i0 + orow;
+        const long long pix = ((long long)tl.b * g.Ho + i) * g.Wo + tl.j0 + 32 * ph + lr;
+        // the epilogue's operands, issued before the next halo (vmcnt retires in issue order)
+        if (c == 3) epi.request(e, g.ldy, pix, i < g.Ho, n0, lh);
         if (s + 2 < steps) hload(hl, s + 2);
         if constexpr ((V & 1) != 0) {
             // explicit software pipeline: tap t + 1's six fragments are read (hand-issued ds_read_b128, so the
@@ -1566,36 +1399,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
         }
         }
         if (c == 3) {
-            if (i < g.Ho) {
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    const int n = n0 + 8 * qd + 4 * lh;
-                    float o[4] = {acc[4 * qd] + ebias[qd].x + eres[qd].x, acc[4 * qd + 1] + ebias[qd].y + eres[qd].y,
-                                  acc[4 * qd + 2] + ebias[qd].z + eres[qd].z, acc[4 * qd + 3] + ebias[qd].w + eres[qd].w};
-                    if (e.out2) st4(e.out2 + pix * e.ldo2 + n, make_float4(o[0], o[1], o[2], o[3]));
-                    if (e.act == HYRES_ACT_RELU) {
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) o[kk] = fmaxf(o[kk], 0.f);
-                    } else if (e.act == HYRES_ACT_PRELU) {
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) o[kk] = o[kk] >= 0.f ? o[kk] : slope * o[kk];
-                    } else if (e.act == HYRES_ACT_RELU_MASK) {
-                        o[0] = emask[qd].x > 0.f ? o[0] : 0.f;
-                        o[1] = emask[qd].y > 0.f ? o[1] : 0.f;
-                        o[2] = emask[qd].z > 0.f ? o[2] : 0.f;
-                        o[3] = emask[qd].w > 0.f ? o[3] : 0.f;
-                    } else if (e.act == HYRES_ACT_PRELU_MASK) {  // as prelu_bwd4_kernel, per element
-                        const float pv[4] = {emask[qd].x, emask[qd].y, emask[qd].z, emask[qd].w};
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) {
-                            if (!(pv[kk] > 0.f)) pslope += pv[kk] * o[kk];
-                            o[kk] = pv[kk] > 0.f ? o[kk] : slope * o[kk];
-                        }
-                    }
-                    st4(a.y + pix * g.ldy + n,
-                        make_float4(o[0] + eold[qd].x, o[1] + eold[qd].y, o[2] + eold[qd].z, o[3] + eold[qd].w));
-                }
-            }
+            epi.apply(acc, e, a.y, g.ldy, pix, i < g.Ho, n0, lh);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         }
@@ -1612,7 +1416,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
     }
     if (e.act == HYRES_ACT_PRELU_MASK) {  // block partial of the slope gradient (every body ended with a barrier)
         float* red = reinterpret_cast<float*>(lds);
-        red[tid] = pslope;
+        red[tid] = epi.pslope;
         __syncthreads();
         for (int k = 256; k > 0; k >>= 1) {
             if (tid < k) red[tid] += red[tid + k];

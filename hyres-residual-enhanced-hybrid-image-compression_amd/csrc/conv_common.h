@@ -1,4 +1,5 @@
-// Internal declarations shared by the convolution (conv.hip) and weight-gradient (wgrad.hip) units.
+// Internal declarations shared by the convolution (conv.hip, ru_fused.hip through halo_common.h) and weight-gradient
+// (wgrad.hip) units.
 #pragma once
 #include "common.h"
 
@@ -31,6 +32,19 @@ inline int num_cus() {
     return cus;
 }
 
+// Buffer resource of an epilogue operand: an absent operand (p == NULL) gets an empty resource, so its loads return
+// 0 without a branch (a load behind a branch is waited on at the join: the epilogue's loads would serialise)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t opnd_rsrc(const void* p, long long bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, p ? (int)std::min<long long>(bytes, 0x7FFFFFF0LL) : 0,
+                                             0x00020000);
+}
+__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
+}
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
+typedef _Float16 halfx4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 halfx8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 
@@ -59,5 +73,14 @@ __device__ __forceinline__ floatx16 bf6_mfma(const bf16x8_t (&a)[3], const bf16x
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
 
+// bf16x6 staging: four fp32 channels split into their three bf16 pieces, one piece per plane (PLANE apart)
+template <int PLANE>
+__device__ __forceinline__ void bf6_put3(__bf16* base, int o, const float4& v) {
+    bf16x4_t h, m, l;
+    bf6_split4(v, h, m, l);
+    *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
+    *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
+    *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
+}
 
 }  // namespace hyres

@@ -23,25 +23,22 @@
 // as usual (hyres_hip.ops.residual_unit_fused): only the re-reads of t1, t2 and x disappear.
 // The fp16 rounding points are the unfused autocast path's (t1, t2 stored fp16; every GEMM on fp16 operands), so the
 // results agree with it up to fp32 summation order (tests/test_ru_fused_gpu.py).
-#include "common.h"
-#include "conv_common.h"
+#include "halo_common.h"
 
 namespace hyres {
 
 namespace {
 
 constexpr int RU_N = 128, RU_M = 64;               // block width N, bottleneck N / 2
-constexpr int RU_R = 4, RU_TW = 64;                 // output tile: 4 rows x 64 pixels
-constexpr int RU_HH = RU_R + 2, RU_HW = RU_TW + 2;  // t1 halo tile 6 x 66
-constexpr int RU_HNPX = RU_HH * RU_HW;              // 396
-constexpr int RU_PB1 = (RU_HNPX + 31) / 32;         // 13 pixel blocks of 32 in phase 1
-constexpr int RU_PH = 40;                           // halves per staged 32-channel row (80 B: conflict-free b128)
-constexpr int RU_TBUF = RU_PB1 * 32 * RU_PH;        // one staging buffer: 416 rows x 40 halves
-constexpr int RU_W2 = 2 * 9 * RU_M * RU_PH;         // W2 [chunk][tap][co][40]
-constexpr int RU_XE = RU_HNPX * 8;                  // x chunk: 396 pixels x 8 half4 (32 channels)
-constexpr int RU_XV = (RU_XE + 511) / 512;          // half4 loads per thread per chunk (7)
+// the output tile (HALO_R x HALO_TW), its 6 x 66 t1 halo (halo_hw(1), halo_npx(1) = 396 pixels) and the 40-half
+// staged rows (HALO_PH): halo_common.h
+constexpr int RU_PB1 = (halo_npx(1) + 31) / 32;     // 13 pixel blocks of 32 in phase 1
+constexpr int RU_TBUF = RU_PB1 * 32 * HALO_PH;      // one staging buffer: 416 rows x 40 halves
+constexpr int RU_W2 = 2 * 9 * RU_M * HALO_PH;       // W2 [chunk][tap][co][40]
+constexpr int RU_XE = halo_elems(1, 8);             // x chunk: 396 pixels x 8 half4 (32 channels)
+constexpr int RU_XV = halo_per_thread(1, 8, 512);   // half4 loads per thread per chunk (7)
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef halfx8_t half8;
 
 __device__ __forceinline__ half8 ld_w8(const float* p) {  // 8 consecutive fp32 weights -> f16 fragment
     const float4 a = ld4(p), b = ld4(p + 4);
@@ -73,27 +70,17 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 31, lh = lane >> 5;
     const int H = a.H, W = a.W;
-    const int nrt = (H + RU_R - 1) / RU_R, nct = W / RU_TW;
-    // tiles walked XCD-contiguously (hardware XCD = blockIdx.x % 8; gridDim.x % 8 == 0): vertically adjacent tiles share
-    // two halo rows of x
-    const int xcd = blockIdx.x & 7, nx = gridDim.x >> 3, jx = blockIdx.x >> 3;
-    const int q = a.ntiles >> 3, r8 = a.ntiles & 7;
-    const int tbeg = xcd * q + min(xcd, r8), tcnt = q + (xcd < r8 ? 1 : 0);
-    const int mytiles = jx < tcnt ? (tcnt - 1 - jx) / nx + 1 : 0;
-    auto tile_of = [&](int k, int& b, int& i0, int& j0) {
-        int l = tbeg + jx + k * nx;
-        const int rt = l % nrt;
-        l /= nrt;
-        const int ct = l % nct;
-        b = l / nct;
-        i0 = rt * RU_R;
-        j0 = ct * RU_TW;
-    };
+    const int nrt = (H + HALO_R - 1) / HALO_R, nct = W / HALO_TW;
+    // tiles walked XCD-contiguously (hardware XCD = blockIdx.x % 8): vertically adjacent tiles share two halo rows of
+    // x. One group of gridDim.x blocks; gridDim.x % 8 == 0 (hyres_ru_fused_f16), so every XCD holds gridDim.x >> 3 of
+    // them, which is what halo_walk's (nb + 7 - xcd) >> 3 gives for a multiple of 8
+    const HaloWalk walk = halo_walk(blockIdx.x, gridDim.x, a.ntiles, nrt, nct);
+    const int mytiles = walk.mytiles;
 
     // ---- weights: W2 -> LDS fp16 [c][t][co][40] (ci = 32c + k); W1 / W3 fragments -> registers (launch-resident)
     for (int f = tid; f < RU_M * RU_M * 9; f += 512) {  // w2[co][ci][t], linear over the PyTorch layout
         const int co = f / (RU_M * 9), rem = f - co * (RU_M * 9), ci = rem / 9, t = rem - ci * 9;
-        W2s[(((ci >> 5) * 9 + t) * RU_M + co) * RU_PH + (ci & 31)] = (_Float16)a.w2[f];
+        W2s[(((ci >> 5) * 9 + t) * RU_M + co) * HALO_PH + (ci & 31)] = (_Float16)a.w2[f];
     }
     const int cb1 = wave & 1;  // phase 1: t1 output-channel block of this wave
     half8 w1f[8];               // W1[32 cb1 + lr][16 s + 8 lh .. +7], s = 0..7 (K = 128)
@@ -109,27 +96,10 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
         (void*)a.x, (short)0, (int)std::min<long long>((long long)a.B * img * 2, 0x7FFFFFF0LL), 0x00020000);
     half4_t xreg[RU_XV];
     auto xload = [&](int k, int c) {  // x chunk c (channels 32c..32c+31) of tile k's halo -> registers
-        int b, i0, j0;
-        tile_of(k, b, i0, j0);
-        const int base = b * (int)img;
-#pragma unroll
-        for (int v = 0; v < RU_XV; ++v) {
-            const int e = tid + 512 * v;
-            const int px = e >> 3, c4 = e & 7;
-            const int hr = px / RU_HW, hc = px - hr * RU_HW;
-            const int ih = i0 - 1 + hr, iw = j0 - 1 + hc;
-            const bool ok = e < RU_XE && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-            const int off = ok ? (base + (ih * W + iw) * RU_N + 32 * c + 4 * c4) * 2 : (int)0x80000000;
-            xreg[v] = __builtin_bit_cast(half4_t, __builtin_amdgcn_raw_buffer_load_b64(xr, off, 0, 0));
-        }
+        const HaloTile tl = walk.tile(k);
+        halo16_load<true, 512>(xreg, xr, tid, RU_XE, tl.i0, tl.j0, H, W, RU_N, tl.b * (int)img + 32 * c);
     };
-    auto xstore = [&](_Float16* buf) {
-#pragma unroll
-        for (int v = 0; v < RU_XV; ++v) {
-            const int e = tid + 512 * v;
-            if (e < RU_XE) *reinterpret_cast<half4_t*>(&buf[(e >> 3) * RU_PH + 4 * (e & 7)]) = xreg[v];
-        }
-    };
+    auto xstore = [&](_Float16* buf) { halo16_store<true, 512>(buf, xreg, tid, RU_XE); };
 
     // phase 1 pixel blocks of this wave: 2 output-channel blocks x 13 pixel blocks over 8 waves
     const int pbase = wave >> 1;  // pixel blocks pbase, pbase + 4, pbase + 8, pbase + 12 (< 13)
@@ -143,8 +113,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
     }
     __syncthreads();
     for (int k = 0; k < mytiles; ++k) {
-        int b, i0, j0;
-        tile_of(k, b, i0, j0);
+        const auto [b, i0, j0] = walk.tile(k);
         // ---------------- phase 1: t1 = relu(W1 x + b1) over the halo
         floatx16 acc1[4];
 #pragma unroll
@@ -161,7 +130,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
                 for (int i = 0; i < 4; ++i) {
                     const int pb = pbase + 4 * i;
                     if (pb < RU_PB1) {
-                        const half8 bf = *reinterpret_cast<const half8*>(&X[(32 * pb + lr) * RU_PH + 16 * ss + 8 * lh]);
+                        const half8 bf = *reinterpret_cast<const half8*>(&X[(32 * pb + lr) * HALO_PH + 16 * ss + 8 * lh]);
                         acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc1[i], 0, 0, 0);
                     }
                 }
@@ -178,11 +147,11 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
             const int pb = pbase + 4 * i;
             if (pb >= RU_PB1) continue;
             const int px = 32 * pb + lr;
-            const int hr = px / RU_HW, hc = px - hr * RU_HW;
+            const int hr = px / halo_hw(1), hc = px - hr * halo_hw(1);
             const int ih = i0 - 1 + hr, iw = j0 - 1 + hc;
-            const bool inside = px < RU_HNPX && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
+            const bool inside = px < halo_npx(1) && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
             // training: the tile's own (center) pixels of t1 also go to HBM — every pixel is the center of one tile
-            const bool center = a.t1 != nullptr && inside && hr >= 1 && hr <= RU_R && hc >= 1 && hc <= RU_TW;
+            const bool center = a.t1 != nullptr && inside && hr >= 1 && hr <= HALO_R && hc >= 1 && hc <= HALO_TW;
             const long long tpix = ((long long)b * H + ih) * W + iw;
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
@@ -192,7 +161,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
                 half4_t h;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) h[r] = (_Float16)(inside ? fmaxf(acc1[i][4 * qd + r] + bv[r], 0.f) : 0.f);
-                *reinterpret_cast<half4_t*>(&T[cb1 * RU_TBUF + px * RU_PH + co]) = h;
+                *reinterpret_cast<half4_t*>(&T[cb1 * RU_TBUF + px * HALO_PH + co]) = h;
                 if (center) *reinterpret_cast<half4_t*>(&a.t1[tpix * RU_M + 32 * cb1 + co]) = h;
             }
         }
@@ -206,17 +175,17 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const _Float16* Hc = T + c * RU_TBUF;
-            const _Float16* Bc = W2s + c * 9 * RU_M * RU_PH;
+            const _Float16* Bc = W2s + c * 9 * RU_M * HALO_PH;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int dh = t / 3 - 1, dw = t % 3 - 1;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const half8 bf = *reinterpret_cast<const half8*>(&Bc[(t * RU_M + wn * 32 + lr) * RU_PH + 16 * ks + 8 * lh]);
+                    const half8 bf = *reinterpret_cast<const half8*>(&Bc[(t * RU_M + wn * 32 + lr) * HALO_PH + 16 * ks + 8 * lh]);
 #pragma unroll
                     for (int at = 0; at < 2; ++at) {
-                        const int px = (orow + 1 + dh) * RU_HW + at * 32 + lr + 1 + dw;
-                        const half8 af = *reinterpret_cast<const half8*>(&Hc[px * RU_PH + 16 * ks + 8 * lh]);
+                        const int px = (orow + 1 + dh) * halo_hw(1) + at * 32 + lr + 1 + dw;
+                        const half8 af = *reinterpret_cast<const half8*>(&Hc[px * HALO_PH + 16 * ks + 8 * lh]);
                         acc2[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, af, acc2[at], 0, 0, 0);
                     }
                 }
@@ -226,7 +195,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
         // t2 epilogue -> T as [chunk = wn][output pixel (orow*64 + 32 at + lr)][40]
 #pragma unroll
         for (int at = 0; at < 2; ++at) {
-            const int px = orow * RU_TW + 32 * at + lr;
+            const int px = orow * HALO_TW + 32 * at + lr;
             const bool store = a.t2 != nullptr && i0 + orow < H;
             const long long tpix = ((long long)b * H + i0 + orow) * W + j0 + 32 * at + lr;
 #pragma unroll
@@ -237,7 +206,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
                 half4_t h;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) h[r] = (_Float16)fmaxf(acc2[at][4 * qd + r] + bv[r], 0.f);
-                *reinterpret_cast<half4_t*>(&T[wn * RU_TBUF + px * RU_PH + co]) = h;
+                *reinterpret_cast<half4_t*>(&T[wn * RU_TBUF + px * HALO_PH + co]) = h;
                 if (store) *reinterpret_cast<half4_t*>(&a.t2[tpix * RU_M + 32 * wn + co]) = h;
             }
         }
@@ -256,7 +225,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_f16_kernel(const RuArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int px = 32 * (pb3 + 2 * i) + lr;
-                const half8 bf = *reinterpret_cast<const half8*>(&Tc[px * RU_PH + 16 * (s & 1) + 8 * lh]);
+                const half8 bf = *reinterpret_cast<const half8*>(&Tc[px * HALO_PH + 16 * (s & 1) + 8 * lh]);
                 acc3[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w3f[s], bf, acc3[i], 0, 0, 0);
             }
         }
@@ -294,7 +263,7 @@ using namespace hyres;
 extern "C" {
 
 int hyres_ru_fused_f16_ok(int B, int H, int W, int N) {
-    return N == RU_N && B > 0 && H > 0 && W > 0 && W % RU_TW == 0 && (long long)B * H * W * RU_N * 2 < 0x7FFFFFF0LL;
+    return N == RU_N && B > 0 && H > 0 && W > 0 && W % HALO_TW == 0 && (long long)B * H * W * RU_N * 2 < 0x7FFFFFF0LL;
 }
 
 int hyres_ru_fused_f16(const void* x, void* y, int B, int H, int W, int N, const float* w1, const float* b1,
@@ -315,7 +284,7 @@ int hyres_ru_fused_f16(const void* x, void* y, int B, int H, int W, int N, const
     a.t1 = (_Float16*)t1;
     a.t2 = (_Float16*)t2;
     a.B = B; a.H = H; a.W = W;
-    a.ntiles = B * ((H + RU_R - 1) / RU_R) * (W / RU_TW);
+    a.ntiles = B * ((H + HALO_R - 1) / HALO_R) * (W / HALO_TW);
     a.final_relu = final_relu ? 1 : 0;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=

@@ -64,8 +64,6 @@ __device__ __forceinline__ void slab_store_acc(const floatx16& acc, float* col, 
 }
 
 typedef __fp16 fp16x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 halfx4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 halfx8_t __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ halfx4_t lds_tr4(const _Float16* p) {
     fp16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_t*)(p));
@@ -80,16 +78,6 @@ __device__ __forceinline__ halfx8_t tr_frag(const _Float16* p, int pitch) {
 }
 __device__ __forceinline__ bf16x8_t tr_frag(const __bf16* p, int pitch) {
     return __builtin_bit_cast(bf16x8_t, tr_frag(reinterpret_cast<const _Float16*>(p), pitch));
-}
-
-// bf16x6 staging: four fp32 channels split into their three bf16 pieces, one piece per plane (PLANE apart)
-template <int PLANE>
-__device__ __forceinline__ void bf6_put3(__bf16* base, int o, const float4& v) {
-    bf16x4_t h, m, l;
-    bf6_split4(v, h, m, l);
-    *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
-    *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
-    *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
 }
 
 }  // namespace hyres

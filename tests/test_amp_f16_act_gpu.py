@@ -367,6 +367,8 @@ LAYER_CASES = [
     ("conv", 2, 64, 3, 16, 64, 3, 1, 1, 1),       # Co = 3: swapped thin weight gradient with a fp16 P
     ("deconv", 2, 128, 128, 16, 32, 5, 2, 2, 1),  # P = x fp16 (g_s)
     ("deconv", 2, 128, 3, 16, 16, 5, 2, 2, 1),    # thin weight gradient with a fp16 P (g_s's last deconv)
+    # conv3x3_wres_f16_kernel's ragged tile walk: 372 tiles (372 % 8 = 4, H % 4 = 2) over 2 channel groups x 128 blocks
+    ("conv", 3, 64, 128, 122, 256, 3, 1, 1, 1),
 ]
 
 

@@ -609,7 +609,8 @@ def test_narrow_strip_kernel_matches_fp64(kind, B, Ci, H, W, f16x):
 
 
 @pytest.mark.parametrize("B,H,W,act", [(4, 128, 128, "relu"), (1, 256, 384, "prelu"), (1, 256, 384, "relu"),
-                                       (4, 128, 128, "prelu"), (2, 128, 256, "prelu")])
+                                       (4, 128, 128, "prelu"), (2, 128, 256, "prelu"),
+                                       (3, 122, 256, "relu")])  # 372 tiles: 372 % 8 = 4, 2 or 3 per block, H % 4 = 2
 def test_wres_bf6_dilation2_matches_fp64(B, H, W, act):
     """The weight-resident bf16x6 3x3 at halo radius 2 (conv3x3_wres_bf6_kernel<true, 1, 2>: MultiScaleRefine's
     dilation-2 convs, enhancement.py:44-51) — forward with residual and the input gradient (a dilation-2 conv over dY)

@@ -81,6 +81,9 @@ CONV_CASES = [
     (2, 64, 64, 128, 256, 3, 1, 1, 1),
     (2, 64, 64, 126, 256, 3, 1, 1, 1),
     (4, 64, 32, 128, 256, 3, 1, 1, 1),
+    # the tile walk's ragged case: 3 x 31 x 4 = 372 tiles (372 % 8 = 4, a partial last row tile) over 2 channel
+    # groups x 128 blocks, so blocks of one launch walk 2 or 3 tiles
+    (3, 64, 64, 122, 256, 3, 1, 1, 1),
 ]
 
 # the weight-gradient kernel the cases above name in their comments, as hyres_wgrad_kernel_name reports it (under
@@ -1881,7 +1884,10 @@ AMP_CASES = [(2, 64, 64, 16, 16, 3, 1, 1, 1), (2, 128, 192, 16, 16, 5, 2, 2, 1),
              # and two 64-channel output groups, a partial last row tile
              (4, 64, 64, 128, 256, 3, 1, 1, 1), (2, 64, 128, 128, 256, 3, 1, 1, 1), (4, 64, 64, 126, 256, 3, 1, 1, 1),
              # >= 65536 pixels, 1x1: the streaming 1x1 kernel on fp16-rounded operands
-             (4, 64, 128, 128, 128, 1, 1, 0, 1), (4, 128, 64, 128, 128, 1, 1, 0, 1)]
+             (4, 64, 128, 128, 128, 1, 1, 0, 1), (4, 128, 64, 128, 128, 1, 1, 0, 1),
+             # conv3x3_wres_f16_kernel's ragged tile walk: 372 tiles (372 % 8 = 4, H % 4 = 2) over 2 channel groups x
+             # 128 blocks, 2 or 3 tiles per block (last, so that the ids above keep their cases)
+             (3, 64, 128, 122, 256, 3, 1, 1, 1)]
 
 
 @pytest.mark.parametrize("case", AMP_CASES)

@@ -43,7 +43,8 @@ def _torch_ru(x, ws, bs, final_relu):
 
 
 @pytest.mark.parametrize("final_relu", [True, False])
-@pytest.mark.parametrize("B,H,W", [(2, 32, 64), (2, 30, 128), (1, 8, 192)])
+@pytest.mark.parametrize("B,H,W", [(2, 32, 64), (2, 30, 128), (1, 8, 192),
+                                   (3, 122, 256)])  # 372 tiles over 256 blocks: one or two tiles per block
 def test_ru_fused_matches_torch_and_unfused(B, H, W, final_relu, monkeypatch):
     from hyres_hip import _lib as L
     from hyres_hip import ops as O
