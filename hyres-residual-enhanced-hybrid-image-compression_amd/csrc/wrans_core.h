@@ -126,7 +126,10 @@ WRANS_HD uint32_t ld32(const unsigned char* p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
-enum HeaderError { kOk = 0, kShort = 1, kBadMagic = 2, kBadCount = 3, kBadLengths = 4, kBadSize = 5 };
+enum HeaderError {
+    kOk = 0, kShort = 1, kBadMagic = 2, kBadCount = 3, kBadLengths = 4, kBadSize = 5,
+    kBadMagic2 = 6, kBadSegments = 7, kBadDirectory = 8  // HRW2 (check_header2)
+};
 
 // a string of ``len`` bytes that is to hold ``n_expected`` coded symbols
 WRANS_HD int check_header(const unsigned char* in, long long len, long long n_expected, Header& h) {
@@ -148,12 +151,70 @@ inline const char* header_error(int e) {
         case kBadCount: return "symbol count disagrees with the latent shape and parity";
         case kBadLengths: return "more escapes or payload words than coded symbols";
         case kBadSize: return "header lengths disagree with the byte count";
+        case kBadMagic2: return "no HRW2 magic (an HRW1 or a host-format string?)";
+        case kBadSegments: return "rows per segment is 0 or the segment count disagrees with the symbol count";
+        case kBadDirectory: return "segment directory decreases or gives a segment more escapes or words than symbols";
         default: return "ok";
     }
 }
 
 // worst case of one string: every symbol an escape and every step a word
 WRANS_HD long long max_string_bytes(long long n) { return kFixedBytes + 8 * n; }
+
+// ---------------------------------------------------------------- HRW2: an HRW1-style string cut into segments
+// One string per image and pass, little endian:
+//   header     "HRW2", uint32 n (coded symbols), uint32 R (rows per segment, >= 1), uint32 S (segments)
+//   directory  S x { uint32 esc_end, uint32 words_end }: cumulative escapes / payload words through segment s
+//   states     S x 64 x uint64, segment-major, lane 0 first
+//   escapes    esc_end[S - 1] x int32, segments ascending (so coded-symbol order overall)
+//   payload    words_end[S - 1] x uint32, segments ascending, HRW1's order within a segment
+// S = max(1, ceil(n / (64 R))); segment s owns the coded symbols [64 R s, min(n, 64 R (s + 1))) and is coded exactly as
+// HRW1 codes a whole string of those symbols: its states, escapes and payload are byte-equal to that string's.
+constexpr uint32_t kMagic2 = 0x32575248u;                  // "HRW2"
+constexpr int kHeader2Words = 4;                           // magic, n, R, S
+constexpr int kSegFixedWords = 2 + 2 * kLanes;             // per segment: directory entry + lane states
+
+WRANS_HD long long seg_symbols(long long R) { return (long long)kLanes * R; }
+WRANS_HD long long segments(long long n, long long R) {
+    const long long q = seg_symbols(R);
+    return n <= q ? 1 : (n + q - 1) / q;
+}
+// coded symbols of segment s
+WRANS_HD long long seg_count(long long n, long long R, long long s) {
+    const long long k0 = seg_symbols(R) * s, k1 = k0 + seg_symbols(R);
+    return k0 >= n ? 0 : (k1 < n ? k1 : n) - k0;
+}
+WRANS_HD long long fixed_words2(long long S) { return kHeader2Words + (long long)kSegFixedWords * S; }
+WRANS_HD long long max_string_bytes2(long long n, long long S) { return 4 * fixed_words2(S) + 8 * n; }
+
+struct Header2 {
+    uint32_t n, R, S, n_esc, n_words;  // n_esc / n_words: the directory's last entry
+};
+
+// a string of ``len`` bytes that is to hold ``n_expected`` coded symbols; fails in the order magic, symbol count,
+// segment geometry, directory, byte count
+WRANS_HD int check_header2(const unsigned char* in, long long len, long long n_expected, Header2& h) {
+    if (len < 4 || ld32(in) != kMagic2) return kBadMagic2;
+    if (len < 4ll * kHeader2Words || (len & 3)) return kBadSize;
+    h.n = ld32(in + 4);
+    h.R = ld32(in + 8);
+    h.S = ld32(in + 12);
+    if ((long long)h.n != n_expected) return kBadCount;
+    if (h.R < 1 || (long long)h.S != segments(h.n, h.R)) return kBadSegments;
+    if (len < 4 * fixed_words2(h.S)) return kBadSize;
+    uint32_t pe = 0, pw = 0;
+    for (long long s = 0; s < (long long)h.S; ++s) {
+        const uint32_t e = ld32(in + 16 + 8 * s), w = ld32(in + 20 + 8 * s);
+        const long long ns = seg_count(h.n, h.R, s);
+        if (e < pe || w < pw || (long long)(e - pe) > ns || (long long)(w - pw) > ns) return kBadDirectory;
+        pe = e;
+        pw = w;
+    }
+    h.n_esc = pe;
+    h.n_words = pw;
+    if (4 * (fixed_words2(h.S) + (long long)pe + pw) != len) return kBadSize;
+    return kOk;
+}
 
 }  // namespace wrans
 }  // namespace hyres

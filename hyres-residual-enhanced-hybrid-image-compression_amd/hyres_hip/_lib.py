@@ -144,6 +144,14 @@ _SIGS = {
     "hyres_wrans_validate": (_I, [_P, _LL, _I, _I, _I, _I]),
     "hyres_wrans_encode_host": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _LL, ctypes.POINTER(_LL)]),
     "hyres_wrans_decode_host": (_I, [_P, _LL, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
+    "hyres_wrans2_segments": (_LL, [_I, _I, _I, _I, _I]),
+    "hyres_wrans2_max_string_bytes": (_LL, [_I, _I, _I, _I, _I]),
+    "hyres_wrans2_workspace_bytes": (_LL, [_I, _I, _I, _I, _I, _I]),
+    "hyres_wrans2_encode": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _LL, _P, _I, _P, _LL, _P]),
+    "hyres_wrans2_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "hyres_wrans2_validate": (_I, [_P, _LL, _I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "hyres_wrans2_encode_host": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _LL, ctypes.POINTER(_LL)]),
+    "hyres_wrans2_decode_host": (_I, [_P, _LL, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "hyres_jpeg_quant_tables": (_I, [_I, _P, _P]),
     "hyres_jpeg_workspace_bytes": (_LL, [_I, _I, _I]),
     "hyres_jpeg_stream_bytes": (_LL, [_I, _I]),

@@ -14,7 +14,9 @@
   ``DeviceDecoder`` code the same symbols with the wave-interleaved format HRW1 (csrc/wrans.hip, one wave per
   string, its own wire format: DESIGN.md "Device rANS coder"). Symbols and indexes stay on the device: compress
   downloads the offset table and the packed bytes, decompress uploads all strings of the call once and queues its
-  decode launches on the stream without a host wait.
+  decode launches on the stream without a host wait. ``seg_rows`` > 0 (``coder_segment_rows``,
+  HYRES_WRANS_SEGMENT_ROWS) writes the segmented format HRW2 instead: R rows per segment, one wave per segment;
+  decompress takes the format and R of each group from its strings.
 """
 from __future__ import annotations
 
@@ -270,6 +272,7 @@ def get_scale_table(min_=0.11, max_=256, levels=64):
 # ------------------------------------------------------------------------------------------ device coder (HRW1)
 CODERS = ("host", "device")
 WRANS_MAGIC = b"HRW1"
+WRANS2_MAGIC = b"HRW2"
 
 
 def coder_from_env() -> bool:
@@ -279,6 +282,23 @@ def coder_from_env() -> bool:
     if coder not in CODERS:
         raise ValueError(f"HYRES_ENTROPY_CODER={coder!r}: 'host' or 'device'")
     return coder == "device"
+
+
+def segment_rows(value=None) -> int:
+    """The ``coder_segment_rows`` switch: 0 is HRW1, R > 0 is HRW2 with R rows per segment. None reads
+    HYRES_WRANS_SEGMENT_ROWS (unset or 0: HRW1); anything but a non-negative integer is refused."""
+    import operator
+    import os
+    what = "coder_segment_rows"
+    if value is None:
+        value, what = os.environ.get("HYRES_WRANS_SEGMENT_ROWS", "0"), "HYRES_WRANS_SEGMENT_ROWS"
+    try:
+        rows = int(value) if isinstance(value, str) else operator.index(value)
+    except (TypeError, ValueError):
+        rows = -1
+    if not 0 <= rows < 2 ** 31:
+        raise ValueError(f"{what}={value!r}: 0 (HRW1) or a positive number of rows per segment (HRW2)")
+    return rows
 
 
 def _tables_dev(model, device):
@@ -318,16 +338,48 @@ def wrans_validate(data: bytes, C: int, H: int, W: int, parity: int) -> None:
         raise ValueError(lib.hyres_last_error_string().decode())
 
 
+def wrans2_max_string_bytes(C: int, H: int, W: int, parity: int, seg_rows: int) -> int:
+    nb = L.load().hyres_wrans2_max_string_bytes(C, H, W, parity, seg_rows)
+    if nb < 0:
+        raise ValueError(f"wrans2: bad latent shape C={C} H={H} W={W} parity={parity} or seg_rows={seg_rows}")
+    return int(nb)
+
+
+def wrans2_validate(data: bytes, C: int, H: int, W: int, parity: int) -> int:
+    """The rows per segment of the HRW2 string ``data`` of a [C,H,W] latent under ``parity``; ValueError if it is
+    not one (host check, no launch)."""
+    lib = L.load()
+    rows = ctypes.c_int(0)
+    if lib.hyres_wrans2_validate(data, len(data), C, H, W, parity, ctypes.byref(rows)) != 0:
+        raise ValueError(lib.hyres_last_error_string().decode())
+    return rows.value
+
+
+def wrans_group_format(strings, C: int, H: int, W: int, parity: int) -> int:
+    """Validates the strings of one group and returns their format: 0 for HRW1, R > 0 for HRW2 with R rows per
+    segment. ValueError for a string of neither format (the message names the magic) or a group that mixes them."""
+    rows = [wrans2_validate(s, C, H, W, parity) if s[:4] == WRANS2_MAGIC else wrans_validate(s, C, H, W, parity) or 0
+            for s in map(bytes, strings)]
+    if len(set(rows)) > 1:
+        raise ValueError(f"wrans: the strings of one group mix formats or rows per segment: {sorted(set(rows))}")
+    return rows[0] if rows else 0
+
+
 class DeviceEncoder:
     """The strings of one compress call: every ``add`` queues an encode + pack launch pair that appends its B
     strings to one device buffer and one offset table (chained on the stream); ``finish`` downloads the offset
     table, then the used prefix of the buffer, and returns the strings group by group."""
 
-    def __init__(self, device, groups):
-        """``groups``: (B, C, H, W, parity) of every ``add`` to come, in order (sizes the buffer once)."""
+    def __init__(self, device, groups, seg_rows: int = 0):
+        """``groups``: (B, C, H, W, parity) of every ``add`` to come, in order (sizes the buffer once); ``seg_rows``:
+        0 writes HRW1, R > 0 HRW2 with R rows per segment."""
         self.device = device
         self.groups = list(groups)
-        cap = sum(B * wrans_max_string_bytes(C, H, W, p) for B, C, H, W, p in self.groups)
+        self.seg_rows = int(seg_rows)
+        if self.seg_rows:
+            cap = sum(B * wrans2_max_string_bytes(C, H, W, p, self.seg_rows) for B, C, H, W, p in self.groups)
+        else:
+            cap = sum(B * wrans_max_string_bytes(C, H, W, p) for B, C, H, W, p in self.groups)
         self.out = torch.empty(cap, dtype=torch.uint8, device=device)
         self.offs = torch.empty(sum(g[0] for g in self.groups) + 1, dtype=torch.int64, device=device)
         self.done = 0  # groups added
@@ -337,14 +389,16 @@ class DeviceEncoder:
         assert self.groups[self.done] == (B, C, H, W, parity), (self.groups[self.done], (B, C, H, W, parity))
         from .ops import Workspace
         lib = L.load()
-        nws = lib.hyres_wrans_workspace_bytes(B, C, H, W, parity)
+        R = self.seg_rows
+        nws = (lib.hyres_wrans2_workspace_bytes(B, C, H, W, parity, R) if R
+               else lib.hyres_wrans_workspace_bytes(B, C, H, W, parity))
         if nws < 0:
             raise ValueError(f"wrans: bad latent shape B={B} C={C} H={H} W={W} parity={parity}")
         ws = Workspace.get(int(nws), self.device, "wrans")
         offs_ptr = self.offs.data_ptr() + 8 * self.nstr
-        L.call("hyres_wrans_encode", sym.data_ptr(), L.ptr(idx), B, C, H, W, parity,
-               *_table_args(_tables_dev(model, self.device)), self.out.data_ptr(), self.out.numel(), offs_ptr,
-               int(self.done > 0), ws.data_ptr(), ws.numel(), L.stream())
+        L.call("hyres_wrans2_encode" if R else "hyres_wrans_encode", sym.data_ptr(), L.ptr(idx), B, C, H, W, parity,
+               *_table_args(_tables_dev(model, self.device)), *([R] if R else []), self.out.data_ptr(),
+               self.out.numel(), offs_ptr, int(self.done > 0), ws.data_ptr(), ws.numel(), L.stream())
         self.done += 1
         self.nstr += B
 
@@ -361,19 +415,20 @@ class DeviceEncoder:
 
 class DeviceDecoder:
     """The strings of one decompress call: validated on the host (ValueError before anything is launched), copied
-    into one pinned buffer with their offset table and uploaded once; ``decode`` then queues one launch per group."""
+    into one pinned buffer with their offset table and uploaded once; ``decode`` then queues one launch per group.
+    Each group's format (HRW1, or HRW2 and its rows per segment) is read from its strings."""
 
     def __init__(self, device, groups, strings):
         """``groups``: (B, C, H, W, parity) per group; ``strings``: the groups' lists of bytes, in the same order."""
         self.device = device
         self.groups = list(groups)
+        self.seg_rows = []  # per group: 0 for HRW1, R for HRW2
         flat = []
         for (B, C, H, W, parity), ss in zip(self.groups, strings):
             ss = resolve(list(ss))
             if len(ss) != B:
                 raise ValueError(f"wrans: {len(ss)} strings for a batch of {B}")
-            for s in ss:
-                wrans_validate(bytes(s), C, H, W, parity)
+            self.seg_rows.append(wrans_group_format(ss, C, H, W, parity))
             flat += ss
         offs = np.zeros(len(flat) + 1, dtype=np.int64)
         np.cumsum([len(s) for s in flat], out=offs[1:])
@@ -392,9 +447,11 @@ class DeviceDecoder:
     def decode(self, k: int, model, idx, params: Node = None, M: int = 0) -> torch.Tensor:
         """Group k -> the full symbol array [B, C*H*W] (int32, device); no host wait."""
         B, C, H, W, parity = self.groups[k]
+        R = self.seg_rows[k]
         sym = torch.empty((B, C * H * W), dtype=torch.int32, device=self.device)
-        L.call("hyres_wrans_decode", self.buf.data_ptr() + self.head, self.buf.data_ptr() + 8 * self.first[k],
-               L.ptr(idx), B, C, H, W, parity, *_table_args(_tables_dev(model, self.device)),
+        L.call("hyres_wrans2_decode" if R else "hyres_wrans_decode", self.buf.data_ptr() + self.head,
+               self.buf.data_ptr() + 8 * self.first[k], L.ptr(idx), B, C, H, W, parity, *([R] if R else []),
+               *_table_args(_tables_dev(model, self.device)),
                None if params is None else params.ptr(), 0 if params is None else params.ld, M, sym.data_ptr(),
                L.stream())
         return sym

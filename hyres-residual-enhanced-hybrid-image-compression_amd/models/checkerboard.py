@@ -42,13 +42,17 @@ class LightWeightCheckerboard(CompressionModel):
     # the reference does; False (default): dequantise the encoded symbols on the device (identical values)
     decode_in_compress = False
 
-    def __init__(self, N=128, M=192, device_coder: Optional[bool] = None):
+    def __init__(self, N=128, M=192, device_coder: Optional[bool] = None, coder_segment_rows: Optional[int] = None):
         """``device_coder``: code the strings on the GPU in the wave-interleaved format HRW1 (hyres_hip/entropy_coding.py
         DeviceEncoder / DeviceDecoder) instead of compressai's format on the host; None takes HYRES_ENTROPY_CODER
-        (host | device, default host). A model on the CPU keeps the host coder either way."""
+        (host | device, default host). A model on the CPU keeps the host coder either way.
+        ``coder_segment_rows``: with the device coder, 0 writes HRW1 and R > 0 the segmented format HRW2 with R rows of
+        64 symbols per segment (one wave per segment; 512 is the recommended value); None takes
+        HYRES_WRANS_SEGMENT_ROWS (default 0). decompress reads either format whatever this is set to."""
         super().__init__()
         self.N, self.M = N, M
         self.device_coder = EC.coder_from_env() if device_coder is None else bool(device_coder)
+        self.coder_segment_rows = EC.segment_rows(coder_segment_rows)
         self.entropy_bottleneck = EntropyBottleneck(N)
         self.gaussian_conditional = GaussianConditional(None)
         self.quantizer = Quantizer()
@@ -159,7 +163,8 @@ class LightWeightCheckerboard(CompressionModel):
         B = z.B
         groups = self._groups(B, z.H, z.W)
         literal = self.decode_in_compress
-        encs = [EC.DeviceEncoder(dev, [g]) for g in groups] if literal else [EC.DeviceEncoder(dev, groups)] * 3
+        R = self.coder_segment_rows
+        encs = [EC.DeviceEncoder(dev, [g], R) for g in groups] if literal else [EC.DeviceEncoder(dev, groups, R)] * 3
         strings = [None, None, None]
         sym = EC.eb_compress_device(eb, z, encs[0])
         if literal:

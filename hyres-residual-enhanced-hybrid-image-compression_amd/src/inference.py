@@ -38,6 +38,10 @@ def parse_args(argv):
     p.add_argument("--entropy-coder", choices=("host", "device"), default=None,
                    help="rANS coder of the residual strings: host (compressai's format) or device (HIP, the "
                         "wave-interleaved format HRW1); default: HYRES_ENTROPY_CODER, else host")
+    p.add_argument("--coder-segment-rows", type=int, default=None, metavar="N",
+                   help="with the device coder: write the segmented format HRW2 with N rows of 64 symbols per "
+                        "segment, one wave per segment (512 is the recommended value); 0: HRW1; default: "
+                        "HYRES_WRANS_SEGMENT_ROWS, else HRW1")
     return p.parse_args(argv)
 
 
@@ -102,7 +106,8 @@ def main(argv):
         raise RuntimeError(f'"{ckpt}" is not a valid file.')
     state_dict = load_checkpoint(ckpt)
     coder = None if args.entropy_coder is None else args.entropy_coder == "device"
-    model = ResidualJPEGCompression(base_model=LightWeightCheckerboard(N=args.N, M=args.M, device_coder=coder),
+    model = ResidualJPEGCompression(base_model=LightWeightCheckerboard(N=args.N, M=args.M, device_coder=coder,
+                                                                       coder_segment_rows=args.coder_segment_rows),
                                     jpeg_quality=args.jpeg_quality)
     model.load_state_dict(state_dict)
     model = model.to(device).eval()

@@ -648,6 +648,48 @@ int hyres_wrans_decode_host(const unsigned char* in, long long in_len, const int
                             const float* params, int ldp, int M, int* sym_out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Segmented device rANS format HRW2 (a second opt-in on top of HRW1): one string is cut into S = max(1, ceil(n / 64R))
+ * segments of R = ``seg_rows`` rows of 64 coded symbols, each coded exactly as HRW1 codes a whole string, so one
+ * wave64 codes one segment and a string takes S waves. "HRW2", n, R, S; S x {esc_end, words_end} (cumulative); S x 64
+ * lane states; the escapes; the payload words (csrc/wrans_core.h). Everything else is as for
+ * hyres_wrans_*: the coded symbols, the arrays, the tables, ``chain``. hyres_wrans_validate refuses an HRW2 string
+ * and hyres_wrans2_validate an HRW1 string. */
+/* ------------------------------------------------------------------------------------------ */
+/* segments of one string, or -1 on a bad shape or seg_rows < 1 (host) */
+long long hyres_wrans2_segments(int C, int H, int W, int parity, int seg_rows);
+/* the most bytes one string can take: 16 + 520 per segment + 8 per coded symbol, or -1 (host) */
+long long hyres_wrans2_max_string_bytes(int C, int H, int W, int parity, int seg_rows);
+/* workspace of hyres_wrans2_encode for B <= 65535 strings, or -1 (host) */
+long long hyres_wrans2_workspace_bytes(int B, int C, int H, int W, int parity, int seg_rows);
+/* As hyres_wrans_encode, in HRW2 with seg_rows rows per segment (out_cap >= B * max_string_bytes behind the start
+ * offset). Three kernels on ``s`` (encode and pack on a (segments, B) grid, a scan of one wave per string between
+ * them), no host sync; bad arguments are refused before any launch. */
+int hyres_wrans2_encode(const int* sym, const int* idx, int B, int C, int H, int W, int parity, const int* cdfs,
+                        int cdf_stride, const int* cdf_sizes, const int* offsets, int ncdf, int seg_rows,
+                        unsigned char* out, long long out_cap, long long* offs, int chain, void* ws, long long ws_bytes,
+                        hyres_stream_t s);
+/* As hyres_wrans_decode for HRW2 strings that all have ``seg_rows`` rows per segment (validate every string with
+ * hyres_wrans2_validate on the host first and compare the R it returns). Grid and loop bounds come from the shape and
+ * seg_rows alone; reads are clamped to each string's end, to the directory's counts and to the tables. One kernel. */
+int hyres_wrans2_decode(const unsigned char* strings, const long long* offs, const int* idx, int B, int C, int H, int W,
+                        int parity, int seg_rows, const int* cdfs, int cdf_stride, const int* cdf_sizes,
+                        const int* offsets, int ncdf, const float* params, int ldp, int M, int* sym_out,
+                        hyres_stream_t s);
+/* one HRW2 string of a [C,H,W] latent under ``parity``: magic, n, R >= 1 and S, a non-decreasing directory whose steps
+ * fit their segments, the byte count (checked in this order); *seg_rows_out (may be NULL) receives R. HYRES_E_ARG with
+ * the reason otherwise (host) */
+int hyres_wrans2_validate(const unsigned char* in, long long in_len, int C, int H, int W, int parity,
+                          int* seg_rows_out);
+/* the same coder on host memory, one string; out == NULL: *out_len only. decode_host validates the string and takes
+ * R from it. No GPU call (host) */
+int hyres_wrans2_encode_host(const int* sym, const int* idx, int C, int H, int W, int parity, const int* cdfs,
+                             int cdf_stride, const int* cdf_sizes, const int* offsets, int ncdf, int seg_rows,
+                             unsigned char* out, long long out_cap, long long* out_len);
+int hyres_wrans2_decode_host(const unsigned char* in, long long in_len, const int* idx, int C, int H, int W,
+                             int parity, const int* cdfs, int cdf_stride, const int* cdf_sizes, const int* offsets,
+                             int ncdf, const float* params, int ldp, int M, int* sym_out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* JPEG 4:2:2 base layer: bit-exact with libjpeg-turbo at PyTurboJPEG's defaults */
 /* ------------------------------------------------------------------------------------------ */
 /* libjpeg's quality-scaled baseline quantisation tables (entries 1..255) in zigzag order, i.e. the two DQT
