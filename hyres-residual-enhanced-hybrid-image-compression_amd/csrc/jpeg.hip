@@ -318,6 +318,285 @@ __global__ __launch_bounds__(kThreads) void jpeg_ff_emit_kernel(const uint32_t* 
     }
 }
 
+// ---------------------------------------------------------------------------------------------- file decode
+// Decoding the entropy segments of foreign 4:2:2 files (the schedule is described in jpeg_core.h):
+//   jpeg_unstuff_count/scan/emit   the reverse of jpeg_ff_*: count the dropped 0x00 of FF 00 pairs per 1 KiB chunk,
+//                         scan, compact into the image's unstuffed bytes; a marker inside the segment sets a flag
+//   jpeg_sync_kernel      one work-group per image, threads strided over the subsequences: round 0, the bounded
+//                         sync rounds, the block-count scan, the write pass and the validity word
+//   jpeg_dc_scan_kernel   inclusive scan of the DC differences per image and component
+//   jpeg_idct_kernel      one 8x8 block per thread: zigzag coefficients * the file's quantiser -> IDCT -> u8 planes
+// and then jpeg_decode_kernel above.
+constexpr int kUnstuffChunk = kThreads * 4;
+constexpr int kSyncThreads = 1024;  // default block of jpeg_sync_kernel (sweep: profiles/jpeg_decode.json)
+constexpr int kMaxSyncThreads = 1024;
+
+__constant__ DecTables d_dec = make_dec_tables();
+
+struct DecLayout {
+    int nb, ucap, nchunks, maxsub;
+    long long ubytes, cnt, bad, ulen, exits, first, coef, yp, cbp, crp, end;
+};
+
+static DecLayout make_dec_layout(int B, int H, int W, long long capacity) {
+    DecLayout L;
+    L.nb = blocks_per_image(H, W);
+    L.ucap = unstuffed_capacity(capacity);
+    L.nchunks = (int)((capacity + kUnstuffChunk - 1) / kUnstuffChunk);
+    L.maxsub = (int)((capacity * 8 + kMinSubBits - 1) / kMinSubBits);
+    long long o = 0;
+    L.ubytes = o, o = align256(o + (long long)B * L.ucap);
+    L.cnt = o, o = align256(o + (long long)B * L.nchunks * 4);
+    L.bad = o, o = align256(o + (long long)B * L.nchunks * 4);
+    L.ulen = o, o = align256(o + (long long)B * 2 * 4);
+    L.exits = o, o = align256(o + (long long)B * 2 * L.maxsub * (long long)sizeof(SubExit));
+    L.first = o, o = align256(o + (long long)B * L.maxsub * 4);
+    L.coef = o, o = align256(o + (long long)B * L.nb * 64 * 2);
+    L.yp = o, o = align256(o + (long long)B * H * W);
+    L.cbp = o, o = align256(o + (long long)B * H * (W / 2));
+    L.crp = o, o = align256(o + (long long)B * H * (W / 2));
+    L.end = o;
+    return L;
+}
+
+// the four segment bytes of thread slot k0 .. k0+3 and the byte before them; -1 past the end
+__device__ __forceinline__ void scan_bytes(const uint8_t* seg, int len, int k0, int* by, int& prev) {
+    prev = k0 > 0 && k0 - 1 < len ? seg[k0 - 1] : 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) by[j] = k0 + j < len ? seg[k0 + j] : -1;
+}
+
+__device__ __forceinline__ int clamped_len(const int* scan_len, int b, int capacity) {
+    const int n = scan_len[b];
+    return n < 0 ? 0 : (n > capacity ? capacity : n);
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_unstuff_count_kernel(const uint8_t* __restrict__ scans,
+                                                                     const long long* __restrict__ scan_off,
+                                                                     const int* __restrict__ scan_len, int capacity,
+                                                                     int nchunks, int* __restrict__ cnt,
+                                                                     int* __restrict__ bad) {
+    __shared__ int sh[kThreads];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int len = clamped_len(scan_len, b, capacity);
+    int by[4], prev, c = 0, e = 0;
+    scan_bytes(scans + scan_off[b], len, chunk * kUnstuffChunk + threadIdx.x * 4, by, prev);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (by[j] < 0) break;
+        c += ff_dropped(prev, by[j]);
+        e |= ff_error(prev, by[j], chunk * kUnstuffChunk + threadIdx.x * 4 + j == len - 1);
+        prev = by[j];
+    }
+    int sum;
+    block_excl_scan(c, sh, sum);
+    e = __syncthreads_or(e);
+    if (threadIdx.x == 0) {
+        cnt[b * nchunks + chunk] = sum;
+        bad[b * nchunks + chunk] = e;
+    }
+}
+
+// one work-group per image: dropped-byte counts -> exclusive offsets in place; ulen[2b] = the unstuffed byte
+// count, ulen[2b+1] = a marker was seen or the segment is longer than the capacity
+__global__ __launch_bounds__(kThreads) void jpeg_unstuff_scan_kernel(int* __restrict__ cnt, const int* __restrict__ bad,
+                                                                    int nchunks, const int* __restrict__ scan_len,
+                                                                    int capacity, int* __restrict__ ulen) {
+    __shared__ int sh[kThreads];
+    const int b = blockIdx.x;
+    int* p = cnt + (long long)b * nchunks;
+    int carry = 0, e = 0;
+    for (int base = 0; base < nchunks; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const int x = i < nchunks ? p[i] : 0;
+        e |= i < nchunks ? bad[(long long)b * nchunks + i] : 0;
+        int sum;
+        const int ex = block_excl_scan(x, sh, sum);
+        if (i < nchunks) p[i] = carry + ex;
+        carry += sum;
+    }
+    e = __syncthreads_or(e);
+    if (threadIdx.x == 0) {
+        ulen[2 * b] = clamped_len(scan_len, b, capacity) - carry;
+        ulen[2 * b + 1] = (e ? kStBadMarker : 0) | (scan_len[b] > capacity || scan_len[b] < 0 ? kStTooLong : 0);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_unstuff_emit_kernel(const uint8_t* __restrict__ scans,
+                                                                    const long long* __restrict__ scan_off,
+                                                                    const int* __restrict__ scan_len, int capacity,
+                                                                    const int* __restrict__ off, int nchunks,
+                                                                    uint8_t* __restrict__ ubytes, int ucap) {
+    __shared__ int sh[kThreads];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int len = clamped_len(scan_len, b, capacity);
+    const int k0 = chunk * kUnstuffChunk + threadIdx.x * 4;
+    int by[4], prev, c = 0;
+    scan_bytes(scans + scan_off[b], len, k0, by, prev);
+    int p = prev;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (by[j] < 0) break;
+        c += ff_dropped(p, by[j]);
+        p = by[j];
+    }
+    int sum;
+    int before = off[b * nchunks + chunk] + block_excl_scan(c, sh, sum);
+    uint8_t* u = ubytes + (long long)b * ucap;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (by[j] < 0) break;
+        if (ff_dropped(prev, by[j])) ++before;
+        else u[k0 + j - before] = (uint8_t)by[j];  // k0 + j - before < len <= capacity < ucap
+        prev = by[j];
+    }
+}
+
+// exclusive scan over blockDim.x (a multiple of 64, <= 1024) threads; the step count is that of the largest block
+// (the steps past blockDim.x add nothing), so that the loop unrolls
+__device__ __forceinline__ int block_excl_scan_n(int v, int* sh, int& total) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    sh[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int off = 1; off < kMaxSyncThreads; off <<= 1) {
+        const int t = tid >= off ? sh[tid - off] : 0;
+        __syncthreads();
+        sh[tid] += t;
+        __syncthreads();
+    }
+    const int incl = sh[tid];
+    total = sh[nt - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(kMaxSyncThreads) void jpeg_sync_kernel(const uint8_t* __restrict__ ubytes, int ucap,
+                                                                   const int* __restrict__ ulen, int sub_bits,
+                                                                   int maxsub, int nb, SubExit* __restrict__ exits,
+                                                                   int* __restrict__ first,
+                                                                   int16_t* __restrict__ coef,
+                                                                   int* __restrict__ status,
+                                                                   int* __restrict__ rounds_out) {
+    __shared__ DecTables T;
+    __shared__ int sh[kMaxSyncThreads];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    for (int i = tid; i < (int)(sizeof(DecTables) / 4); i += nt)
+        reinterpret_cast<uint32_t*>(&T)[i] = reinterpret_cast<const uint32_t*>(&d_dec)[i];
+    __syncthreads();
+    const BitReader R{ubytes + (long long)b * ucap, (uint32_t)ulen[2 * b]};
+    const uint32_t total_bits = R.nbytes * 8u;
+    int nsub = sub_count(total_bits, sub_bits);
+    if (nsub > maxsub) nsub = maxsub;  // cannot happen: ulen <= capacity
+    SubExit* cur = exits + (long long)b * 2 * maxsub;
+    SubExit* nxt = cur + maxsub;
+    coef += (long long)b * nb * 64;
+    first += (long long)b * maxsub;
+
+    for (int i = tid; i < nsub; i += nt) cur[i] = sync_round0(T, R, i, sub_bits, total_bits);
+    __syncthreads();
+    int rounds = 0;
+    for (int r = 1; r < nsub; ++r) {  // bounded: subsequences 0..r are exact after round r
+        int changed = 0;
+        for (int i = tid; i < nsub; i += nt) changed |= sync_round(T, R, i, sub_bits, total_bits, cur, nxt);
+        ++rounds;
+        SubExit* t = cur;
+        cur = nxt;
+        nxt = t;
+        if (!__syncthreads_or(changed)) break;
+    }
+
+    int carry = 0, err = 0;
+    for (int base = 0; base < nsub; base += nt) {
+        const int i = base + tid;
+        const int n = i < nsub ? (int)(cur[i].w >> 16) : 0;
+        if (i < nsub) err |= (int)(cur[i].w & kExitError);
+        int sum;
+        const int e = block_excl_scan_n(n, sh, sum);
+        if (i < nsub) first[i] = carry + e;
+        carry += sum;
+    }
+    for (int i = tid; i < nsub; i += nt) write_subsequence(T, R, i, sub_bits, total_bits, cur, first[i], coef, nb);
+    err = __syncthreads_or(err);
+    if (tid == 0) {
+        status[b] = ulen[2 * b + 1] |
+                    decode_status(R, total_bits, nsub, nsub ? cur[nsub - 1] : SubExit{0u, 0u}, carry, nb, err != 0, false);
+        if (rounds_out) rounds_out[b] = rounds;
+    }
+}
+
+// grid (3, B): component comp of image b, DC differences -> DC values in place
+__global__ __launch_bounds__(kThreads) void jpeg_dc_scan_kernel(int16_t* __restrict__ coef, int nb,
+                                                               const int* __restrict__ status) {
+    __shared__ int sh[kThreads];
+    const int comp = blockIdx.x, b = blockIdx.y;
+    if (status[b]) return;  // uniform over the work-group
+    int16_t* img = coef + (long long)b * nb * 64;
+    const int n = dc_blocks_of(comp, nb);
+    int carry = 0;
+    for (int base = 0; base < n; base += kThreads) {
+        const int s = base + threadIdx.x;
+        int16_t* slot = img + (long long)dc_block_of(comp, s < n ? s : 0) * 64;
+        const int x = s < n ? (int)*slot : 0;
+        int sum;
+        const int e = block_excl_scan(x, sh, sum);
+        if (s < n) *slot = (int16_t)(carry + e + x);
+        carry += sum;
+    }
+}
+
+// grid (ceil(nb / 256), B); item i of an image as in jpeg_blocks_kernel (luminance blocks in raster order first)
+__global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const int16_t* __restrict__ coef,
+                                                            const uint8_t* __restrict__ qtabs,
+                                                            const int* __restrict__ status, int H, int W,
+                                                            uint8_t* __restrict__ yp, uint8_t* __restrict__ cbp,
+                                                            uint8_t* __restrict__ crp) {
+    __shared__ uint16_t q[128];
+    const int b = blockIdx.y;
+    if (status[b]) return;  // uniform over the work-group: the image's output stays unspecified
+    if (threadIdx.x < 128)
+        q[(threadIdx.x & 64) + kNatural[threadIdx.x & 63]] = qtabs[(long long)b * 128 + threadIdx.x];
+    __syncthreads();
+    const int mw = W / 16, nmcu = mw * (H / 8), nb = 4 * nmcu;
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= nb) return;
+    int comp, bx, by, blk;
+    if (i < 2 * nmcu) {
+        comp = 0, bx = i % (2 * mw), by = i / (2 * mw);
+        blk = (by * mw + (bx >> 1)) * 4 + (bx & 1);
+    } else {
+        comp = i < 3 * nmcu ? 1 : 2;
+        const int m = i - (comp + 1) * nmcu;
+        bx = m % mw, by = m / mw;
+        blk = m * 4 + comp + 1;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(coef + ((long long)b * nb + blk) * 64);
+    int16_t zz[64];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        const uint4 v = src[g];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            zz[8 * g + 2 * j] = (int16_t)(w[j] & 0xFFFFu);
+            zz[8 * g + 2 * j + 1] = (int16_t)(w[j] >> 16);
+        }
+    }
+    int d[64];
+    coef_block_to_samples(zz, q + (comp ? 64 : 0), d);
+    const int pw = comp ? W / 2 : W;
+    uint8_t* plane = (comp == 0 ? yp : (comp == 1 ? cbp : crp)) + (long long)b * H * pw;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        uint32_t u[8];  // samples in 0..255
+#pragma unroll
+        for (int c = 0; c < 8; ++c) u[c] = (uint32_t)d[r * 8 + c];
+        const uint32_t lo = u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24);
+        const uint32_t hi = u[4] | (u[5] << 8) | (u[6] << 16) | (u[7] << 24);
+        *reinterpret_cast<uint2*>(plane + (long long)(by * 8 + r) * pw + bx * 8) = make_uint2(lo, hi);
+    }
+}
+
 static int check_shape(const char* what, int B, int H, int W) {
     HY_REQUIRE(B >= 1 && H >= 8 && W >= 16 && H % 8 == 0 && W % 16 == 0 && H <= 65528 && W <= 65520, HYRES_E_SHAPE,
                "%s: B >= 1, H %% 8 == 0, W %% 16 == 0, H, W < 65536 (got %d x %d x %d)", what, B, H, W);
@@ -419,6 +698,106 @@ int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, 
     for (int b = 0; b < B; ++b) {
         sizes[b] = roundtrip_image_host(x + b * img, H, W, quality, decoded + b * img, &f);
         if (files) std::memcpy(files + b * file_stride, f.data(), f.size());
+    }
+    return ok();
+}
+
+int hyres_jpeg_parse(const unsigned char* file, long long nbytes, hyres_jpeg_info* info) {
+    HY_REQUIRE(file && info && nbytes >= 0, HYRES_E_ARG, "jpeg_parse: NULL");
+    FileInfo fi{};
+    const char* why = parse_file(file, (size_t)nbytes, &fi);
+    if (!why && check_shape("jpeg_parse", 1, fi.H, fi.W)) why = "size outside the codec's limits";
+    if (!why && fi.scan_len >= (1LL << 28)) why = "entropy segment of 256 MiB or more";
+    info->supported = why ? 0 : 1;
+    if (why) {
+        set_error(HYRES_E_ARG, "jpeg_parse: %s", why);  // the reason, read through hyres_last_error_string
+        return ok();  // an unsupported file is an answer, not a failed call
+    }
+    info->H = fi.H, info->W = fi.W;
+    info->scan_off = fi.scan_off, info->scan_len = fi.scan_len;
+    std::memcpy(info->qtab, fi.qtab, 128);
+    return ok();
+}
+
+static int check_decode(const char* what, int B, int H, int W, long long capacity, int& sub_bits) {
+    int rc = check_shape(what, B, H, W);
+    if (rc) return rc;
+    HY_REQUIRE(capacity >= 1 && capacity < (1LL << 28), HYRES_E_SHAPE, "%s: scan capacity %lld outside 1 .. 2^28 - 1",
+               what, capacity);
+    if (sub_bits == 0) sub_bits = kDefaultSubBits;
+    HY_REQUIRE(sub_bits >= kMinSubBits && sub_bits <= kMaxSubBits && sub_bits % 32 == 0, HYRES_E_ARG,
+               "%s: sub_bits %d: 0 or a multiple of 32 in 32 .. 8192", what, sub_bits);
+    return ok();
+}
+
+long long hyres_jpeg_decode_workspace_bytes(int B, int H, int W, long long scan_capacity) {
+    int sub = 0;
+    if (check_decode("jpeg_decode_workspace_bytes", B, H, W, scan_capacity, sub)) return -1;
+    return make_dec_layout(B, H, W, scan_capacity).end;
+}
+
+int hyres_jpeg_decode(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                      const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                      int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                      hyres_stream_t s) {
+    HY_REQUIRE(scans && scan_off && scan_len && qtabs && decoded && status, HYRES_E_ARG, "jpeg_decode: NULL");
+    int rc = check_decode("jpeg_decode", B, H, W, scan_capacity, sub_bits);
+    if (rc) return rc;
+    if (block_threads == 0) block_threads = kSyncThreads;
+    HY_REQUIRE(block_threads >= 64 && block_threads <= kMaxSyncThreads && block_threads % 64 == 0, HYRES_E_ARG,
+               "jpeg_decode: block_threads %d: 0 or a multiple of 64 in 64 .. 1024", block_threads);
+    const DecLayout L = make_dec_layout(B, H, W, scan_capacity);
+    HY_REQUIRE(ws && ws_bytes >= L.end, HYRES_E_WORKSPACE, "jpeg_decode: workspace %lld < %lld", ws_bytes, L.end);
+    HY_REQUIRE(aligned16(ws) && aligned16(decoded), HYRES_E_ALIGN, "jpeg_decode: alignment");
+    char* base = (char*)ws;
+    uint8_t* ubytes = (uint8_t*)(base + L.ubytes);
+    int *cnt = (int*)(base + L.cnt), *bad = (int*)(base + L.bad), *ulen = (int*)(base + L.ulen);
+    int* first = (int*)(base + L.first);
+    SubExit* exits = (SubExit*)(base + L.exits);
+    int16_t* coef = (int16_t*)(base + L.coef);
+    uint8_t *yp = (uint8_t*)(base + L.yp), *cbp = (uint8_t*)(base + L.cbp), *crp = (uint8_t*)(base + L.crp);
+    hipStream_t st = as_stream(s);
+    const int cap = (int)scan_capacity;
+    // exits are laid out for the smallest sub_bits; this call uses the first maxsub entries of each buffer
+    const int maxsub = (int)((scan_capacity * 8 + sub_bits - 1) / sub_bits);
+
+    hipLaunchKernelGGL(jpeg_unstuff_count_kernel, dim3(L.nchunks, B), dim3(kThreads), 0, st, scans, scan_off, scan_len,
+                       cap, L.nchunks, cnt, bad);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_unstuff_count"))) return rc;
+    hipLaunchKernelGGL(jpeg_unstuff_scan_kernel, dim3(B), dim3(kThreads), 0, st, cnt, bad, L.nchunks, scan_len, cap,
+                       ulen);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_unstuff_scan"))) return rc;
+    hipLaunchKernelGGL(jpeg_unstuff_emit_kernel, dim3(L.nchunks, B), dim3(kThreads), 0, st, scans, scan_off, scan_len,
+                       cap, cnt, L.nchunks, ubytes, L.ucap);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_unstuff_emit"))) return rc;
+    hipLaunchKernelGGL(jpeg_sync_kernel, dim3(B), dim3(block_threads), 0, st, ubytes, L.ucap, ulen, sub_bits, maxsub,
+                       L.nb, exits, first, coef, status, rounds);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_sync"))) return rc;
+    hipLaunchKernelGGL(jpeg_dc_scan_kernel, dim3(3, B), dim3(kThreads), 0, st, coef, L.nb, status);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_dc_scan"))) return rc;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(ceil_div(L.nb, kThreads), B), dim3(kThreads), 0, st, coef, qtabs, status,
+                       H, W, yp, cbp, crp);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_idct"))) return rc;
+    hipLaunchKernelGGL(jpeg_decode_kernel, dim3(ceil_div((long long)B * H * (W / 2), kThreads)), dim3(kThreads), 0, st,
+                       yp, cbp, crp, B, H, W, decoded);
+    if ((rc = HY_LAUNCH_CHECK("jpeg_decode"))) return rc;
+    return ok();
+}
+
+int hyres_jpeg_decode_host(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                           const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                           int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                           hyres_stream_t s) {
+    (void)block_threads, (void)ws, (void)ws_bytes, (void)s;
+    HY_REQUIRE(scans && scan_off && scan_len && qtabs && decoded && status, HYRES_E_ARG, "jpeg_decode_host: NULL");
+    int rc = check_decode("jpeg_decode_host", B, H, W, scan_capacity, sub_bits);
+    if (rc) return rc;
+    const long long img = 3LL * H * W;
+    for (int b = 0; b < B; ++b) {
+        uint8_t qz[2][64];
+        std::memcpy(qz, qtabs + (long long)b * 128, 128);
+        status[b] = decode_image_host(scans + scan_off[b], scan_len[b], scan_capacity, qz, H, W, sub_bits,
+                                      decoded + b * img, rounds ? rounds + b : nullptr);
     }
     return ok();
 }

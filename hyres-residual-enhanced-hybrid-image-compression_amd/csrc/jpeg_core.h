@@ -13,6 +13,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <utility>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -398,6 +399,236 @@ struct CountSink {
     JC_HD void put(uint32_t, int n) { bits += n; }
 };
 
+// ---------------------------------------------------------------------------------------------- entropy decoding
+// Self-synchronising parallel Huffman decoder (Klein & Wiseman 2003; Weissenberger & Schmidt 2018).  The unstuffed
+// entropy segment of an image is cut into subsequences of sub_bits bits; one thread (device) or loop iteration
+// (host twin) owns a subsequence.  The decoder state between two symbols is (p, c, z): bit position, block-in-MCU
+// 0..3 (0, 1 luminance tables / component Y, 2 Cb, 3 Cr) and the next zigzag index 0..63.
+//   round 0   every subsequence i > 0 decodes from its first bit with the guess (c, z) = (0, 0), subsequence 0 from
+//             the true start, until the next symbol would start in the following subsequence; it records its exit;
+//   round k   subsequence i decodes again from subsequence i-1's exit of round k-1 (two exit buffers, swapped per
+//             round) and reports whether its own exit changed.  A subsequence whose entry did not change in the
+//             previous round keeps its exit without decoding.  Subsequences 0..k are exact after round k, so at
+//             most nsub-1 rounds run; a round in which no exit changed ends the loop early;
+//   write     exclusive scan of the blocks completed per subsequence, then one more decode per subsequence from
+//             the settled entry that stores every coefficient slot (zeros of runs, EOB fills and ZRLs included)
+//             exactly once.  DC slots hold the difference; dc_scan_component turns them into values.
+// decode_symbol is total: any 32 bits at any (c, z) give a next state, consume 2..26 bits and index inside the
+// tables; an invalid code or a run past index 63 sets the error flag.  Speculative rounds feed it garbage.
+
+// libjpeg's jpeg_make_d_derived_tbl for the Annex K tables: t = 0 DC luminance, 1 DC chrominance, 2 AC luminance,
+// 3 AC chrominance.  lut: the next 8 bits -> (code length << 8) | symbol, or 0 where the code is longer than 8 bits.
+struct DecTables {
+    uint16_t lut[4][256];
+    int32_t maxcode[4][17];    // largest code of length l, or -1
+    int32_t valoffset[4][17];  // vals index of the first code of length l, minus that code
+    uint8_t vals[4][256];      // symbols in code order, zero padded: any 8-bit index is inside
+};
+
+constexpr DecTables make_dec_tables() {
+    DecTables t{};
+    for (int k = 0; k < 4; ++k) {
+        const int c = k & 1, ac = k >> 1;
+        const uint8_t* bits = ac ? kAcBits[c] : kDcBits[c];
+        int code = 0, p = 0;
+        for (int l = 1; l <= 16; ++l) {
+            t.valoffset[k][l] = p - code;
+            for (int i = 0; i < bits[l - 1]; ++i, ++p, ++code) {
+                const uint8_t sym = ac ? kAcVals[c][p] : kDcVals[p];
+                t.vals[k][p] = sym;
+                if (l <= 8)
+                    for (int f = 0; f < (1 << (8 - l)); ++f)
+                        t.lut[k][(code << (8 - l)) | f] = (uint16_t)((l << 8) | sym);
+            }
+            t.maxcode[k][l] = bits[l - 1] ? code - 1 : -1;
+            code <<= 1;
+        }
+    }
+    return t;
+}
+
+// MSB-first reader over the unstuffed segment; bits past the end read as ones (the padding value)
+struct BitReader {
+    const uint8_t* bytes;
+    uint32_t nbytes;
+    JC_HD uint32_t word(uint32_t w) const {
+        const uint32_t o = w * 4u;
+        if (o + 4u <= nbytes) {
+            uint32_t v;
+            __builtin_memcpy(&v, bytes + o, 4);
+            return __builtin_bswap32(v);
+        }
+        uint32_t v = 0xFFFFFFFFu;
+        for (uint32_t j = 0; j < 4u; ++j)
+            if (o + j < nbytes) v = (v & ~(0xFFu << (24 - 8 * j))) | ((uint32_t)bytes[o + j] << (24 - 8 * j));
+        return v;
+    }
+    // bits p .. p+31
+    JC_HD uint32_t peek(uint32_t p) const {
+        const uint32_t w = p >> 5, sh = p & 31u;
+        const uint32_t hi = word(w);
+        return sh ? (hi << sh) | (word(w + 1u) >> (32u - sh)) : hi;
+    }
+};
+
+constexpr uint32_t kSymError = 1u, kSymBlockDone = 2u;
+
+// One symbol at bit p in state cz = c * 64 + z.  WRITE: its coefficients go to blk[z ..] (64 zigzag slots of the
+// current block; NULL when that block lies past the image).  Returns kSymError | kSymBlockDone flags.
+template <bool WRITE>
+JC_HD uint32_t decode_symbol(const DecTables& T, const BitReader& R, uint32_t& p, uint32_t& cz, int16_t* blk) {
+    const uint32_t c = (cz >> 6) & 3u;
+    int z = (int)(cz & 63u);
+    const int t = (z ? 2 : 0) + (c >> 1);
+    const uint32_t w = R.peek(p);
+    uint32_t flags = 0;
+    int len, sym;
+    const uint32_t e = T.lut[t][w >> 24];
+    if (e) {
+        len = (int)(e >> 8);
+        sym = (int)(e & 255u);
+    } else {
+        len = 9;
+        while (len <= 16 && (int32_t)(w >> (32 - len)) > T.maxcode[t][len]) ++len;
+        if (len > 16) {  // no such code
+            len = 16;
+            sym = 0;
+            flags = kSymError;
+        } else {
+            sym = T.vals[t][((int32_t)(w >> (32 - len)) + T.valoffset[t][len]) & 255];
+        }
+    }
+    const int s = sym & 15;  // magnitude category: <= 11 for DC, <= 10 for AC in the Annex K tables
+    int v = 0;
+    if (s) {
+        v = (int)((w << len) >> (32 - s));
+        if (v < (1 << (s - 1))) v -= (1 << s) - 1;
+    }
+    p += (uint32_t)(len + s);
+    if (z == 0) {
+        if (WRITE && blk) blk[0] = (int16_t)v;
+        z = 1;
+    } else if (s == 0) {
+        const int end = (sym >> 4) == 15 ? z + 16 : 64;  // ZRL, else EOB
+        if (end > 64) flags |= kSymError;
+        if (WRITE && blk)
+            for (int k = z; k < (end < 64 ? end : 64); ++k) blk[k] = 0;
+        z = end;
+    } else {
+        const int at = z + (sym >> 4);
+        if (at > 63) flags |= kSymError;
+        if (WRITE && blk) {
+            for (int k = z; k < (at < 64 ? at : 64); ++k) blk[k] = 0;
+            if (at <= 63) blk[at] = (int16_t)v;
+        }
+        z = at + 1;
+    }
+    if (z >= 64) {
+        cz = ((c + 1u) & 3u) << 6;
+        flags |= kSymBlockDone;
+    } else {
+        cz = (c << 6) | (uint32_t)z;
+    }
+    return flags;
+}
+
+// exit of a subsequence: p, and w = cz (bits 0..7) | error (8) | exit changed in this round (9) | n << 16, n = the
+// blocks completed by symbols that started in the subsequence (<= sub_bits / 4 + 1 < 65536)
+struct SubExit {
+    uint32_t p, w;
+};
+constexpr uint32_t kExitError = 1u << 8, kExitChanged = 1u << 9;
+constexpr int kMinSubBits = 32, kMaxSubBits = 8192, kDefaultSubBits = 512;
+
+JC_HD int sub_count(uint32_t total_bits, int sub_bits) { return (int)((total_bits + (uint32_t)sub_bits - 1u) / (uint32_t)sub_bits); }
+
+// decodes the symbols that start in subsequence i from the entry (p, cz).  WRITE: first = the index of the block
+// open at the entry, coef = the image's [nb][64] coefficients.
+template <bool WRITE>
+JC_HD SubExit decode_subsequence(const DecTables& T, const BitReader& R, int i, int sub_bits, uint32_t total_bits,
+                                 uint32_t p, uint32_t cz, int16_t* coef, int first, int nb) {
+    const uint32_t lim = (uint32_t)(i + 1) * (uint32_t)sub_bits;
+    const uint32_t end = lim < total_bits ? lim : total_bits;
+    uint32_t err = 0, n = 0;
+    while (p < end) {
+        // fewer than 8 one-bits up to the end of the segment are the padding, not a symbol (no code is all ones)
+        const uint32_t left = total_bits - p;
+        if (left < 8u && (R.peek(p) >> (32u - left)) == (1u << left) - 1u) break;
+        int16_t* blk = nullptr;
+        if (WRITE && first + (int)n < nb) blk = coef + (long long)(first + (int)n) * 64;
+        const uint32_t f = decode_symbol<WRITE>(T, R, p, cz, blk);
+        err |= f & kSymError;
+        n += (f >> 1) & 1u;
+    }
+    return SubExit{p, cz | (err ? kExitError : 0u) | (n << 16)};
+}
+
+JC_HD SubExit sync_round0(const DecTables& T, const BitReader& R, int i, int sub_bits, uint32_t total_bits) {
+    SubExit e = decode_subsequence<false>(T, R, i, sub_bits, total_bits, (uint32_t)i * (uint32_t)sub_bits, 0u, nullptr,
+                                          0, 0);
+    e.w |= kExitChanged;
+    return e;
+}
+
+// round k >= 1 of subsequence i: rd = the exits of round k-1, wr = this round's.  Returns whether the exit changed.
+JC_HD bool sync_round(const DecTables& T, const BitReader& R, int i, int sub_bits, uint32_t total_bits,
+                      const SubExit* rd, SubExit* wr) {
+    SubExit mine = rd[i];
+    mine.w &= ~kExitChanged;
+    if (i == 0 || !(rd[i - 1].w & kExitChanged)) {  // the same entry as in the previous round
+        wr[i] = mine;
+        return false;
+    }
+    const SubExit in = rd[i - 1];
+    SubExit e = decode_subsequence<false>(T, R, i, sub_bits, total_bits, in.p, in.w & 255u, nullptr, 0, 0);
+    const bool changed = e.p != mine.p || ((e.w ^ mine.w) & 255u);
+    if (changed) e.w |= kExitChanged;
+    wr[i] = e;
+    return changed;
+}
+
+JC_HD void write_subsequence(const DecTables& T, const BitReader& R, int i, int sub_bits, uint32_t total_bits,
+                             const SubExit* ex, int first, int16_t* coef, int nb) {
+    const uint32_t p = i ? ex[i - 1].p : 0u, cz = i ? ex[i - 1].w & 255u : 0u;
+    decode_subsequence<true>(T, R, i, sub_bits, total_bits, p, cz, coef, first, nb);
+}
+
+constexpr int kStBadMarker = 1, kStBadSymbol = 2, kStBlockCount = 4, kStBadEnd = 8, kStTooLong = 16;
+
+// validity of a decoded image: last = the final subsequence's exit (nsub > 0), blocks = the blocks completed
+JC_HD int decode_status(const BitReader& R, uint32_t total_bits, int nsub, SubExit last, int blocks, int nb,
+                        bool sym_error, bool marker_error) {
+    int st = marker_error ? kStBadMarker : 0;
+    if (sym_error) st |= kStBadSymbol;
+    if (nsub <= 0) return st | kStBlockCount | kStBadEnd;
+    if (blocks != nb || (last.w & 255u) != 0u) st |= kStBlockCount;
+    // the final position lies within the last byte and the padding bits up to its end are ones
+    if (last.p > total_bits || last.p + 8u <= total_bits) {
+        st |= kStBadEnd;
+    } else {
+        const uint32_t k = total_bits - last.p;
+        if (k && (R.peek(last.p) >> (32u - k)) != (1u << k) - 1u) st |= kStBadEnd;
+    }
+    return st;
+}
+
+// Unstuffing: in an entropy segment every 0xFF is followed by a 0x00 that is dropped; anything else after a 0xFF
+// (a marker), or a 0xFF as the last byte, is an error.  prev = the byte before cur (0 for the first byte).
+JC_HD bool ff_dropped(int prev, int cur) { return prev == 0xFF && cur == 0; }
+JC_HD bool ff_error(int prev, int cur, bool last) { return (prev == 0xFF && cur != 0) || (last && cur == 0xFF); }
+
+// inclusive scan of the DC differences of one component in scan order: Y = blocks 4m, 4m+1, Cb 4m+2, Cr 4m+3.
+// seq = the block's index within its component.
+JC_HD int dc_block_of(int comp, int seq) { return comp == 0 ? (seq >> 1) * 4 + (seq & 1) : seq * 4 + comp + 1; }
+JC_HD int dc_blocks_of(int comp, int nb) { return comp == 0 ? nb / 2 : nb / 4; }
+
+// IDCT of one block from its zigzag coefficients: * the file's quantiser (natural order) -> samples 0..255 in d
+JC_HD void coef_block_to_samples(const int16_t* zz, const uint16_t* q, int* d) {
+#pragma unroll
+    for (int k = 0; k < 64; ++k) d[kNatural[k]] = zz[k];
+    dequant_idct(d, q);
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 // the 623-byte header Pillow / libjpeg write for this configuration (quant tables in zigzag order)
 inline void build_header(const uint8_t lum[64], const uint8_t chr[64], int H, int W, uint8_t* out) {
@@ -450,6 +681,27 @@ struct ByteSink {
     }
 };
 
+// u8 Y [H][W] and Cb / Cr [H][W/2] planes -> fancy upsample, colour, / 255 into planar [3][H][W] (plane 0 = B)
+inline void planes_to_pixels_host(const uint8_t* yp, const uint8_t* cbp, const uint8_t* crp, int H, int W,
+                                  float* decoded) {
+    const int cw = W / 2;
+    const size_t plane = (size_t)H * W;
+    for (int r = 0; r < H; ++r)
+        for (int i = 0; i < cw; ++i) {
+            int cb[2], cr[2];
+            upsample_pair(cbp + (size_t)r * cw, cw, i, cb[0], cb[1]);
+            upsample_pair(crp + (size_t)r * cw, cw, i, cr[0], cr[1]);
+            for (int h = 0; h < 2; ++h) {
+                int R, G, B;
+                const size_t o = (size_t)r * W + 2 * i + h;
+                ycc_to_rgb(yp[o], cb[h], cr[h], R, G, B);
+                decoded[o] = (float)B / 255.0f;
+                decoded[plane + o] = (float)G / 255.0f;
+                decoded[2 * plane + o] = (float)R / 255.0f;
+            }
+        }
+}
+
 // Encode -> decode of one image on the host.  x planar [3][H][W] (plane 0 = B); decoded the same layout;
 // file (optional) receives the complete JPEG file.  Returns the file's byte count.
 inline int roundtrip_image_host(const float* x, int H, int W, int quality, float* decoded,
@@ -476,21 +728,7 @@ inline int roundtrip_image_host(const float* x, int H, int W, int quality, float
         for (int r = 0; r < 8; ++r)
             for (int c = 0; c < 8; ++c) plane[(size_t)(my * 8 + r) * pw + bx * 8 + c] = (uint8_t)d[r * 8 + c];
     }
-    const size_t plane = (size_t)H * W;
-    for (int r = 0; r < H; ++r)
-        for (int i = 0; i < cw; ++i) {
-            int cb[2], cr[2];
-            upsample_pair(cp[0].data() + (size_t)r * cw, cw, i, cb[0], cb[1]);
-            upsample_pair(cp[1].data() + (size_t)r * cw, cw, i, cr[0], cr[1]);
-            for (int h = 0; h < 2; ++h) {
-                int R, G, B;
-                const size_t o = (size_t)r * W + 2 * i + h;
-                ycc_to_rgb(yp[o], cb[h], cr[h], R, G, B);
-                decoded[o] = (float)B / 255.0f;
-                decoded[plane + o] = (float)G / 255.0f;
-                decoded[2 * plane + o] = (float)R / 255.0f;
-            }
-        }
+    planes_to_pixels_host(yp.data(), cp[0].data(), cp[1].data(), H, W, decoded);
     std::vector<uint8_t> local;
     std::vector<uint8_t>& f = file ? *file : local;
     f.clear();
@@ -508,6 +746,194 @@ inline int roundtrip_image_host(const float* x, int H, int W, int quality, float
     f.push_back(0xFF);
     f.push_back(0xD9);
     return (int)f.size();
+}
+
+// What the device decoder needs from a file's marker segments
+struct FileInfo {
+    int H, W;
+    long long scan_off, scan_len;  // the entropy-coded segment: after the SOS header, before the trailing EOI
+    uint8_t qtab[2][64];           // luminance / chrominance quantiser, zigzag order
+};
+
+// Parses the marker segments of a JPEG file.  Returns NULL when the decoder takes the file (baseline 8-bit 4:2:2,
+// three components in one interleaved scan, the Annex K Huffman tables, no restart interval, whole MCUs; APPn / COM
+// segments anywhere), else the reason it does not.
+inline const char* parse_file(const uint8_t* f, size_t n, FileInfo* info) {
+    if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return "not a JPEG file (no SOI)";
+    uint8_t qt[4][64];
+    bool have_qt[4] = {false, false, false, false}, have_ht[2][2] = {{false, false}, {false, false}}, sof = false;
+    int ids[3] = {0, 0, 0}, tq[3] = {0, 0, 0};
+    size_t i = 2;
+    for (;;) {
+        if (i + 4 > n) return "truncated before the scan";
+        if (f[i] != 0xFF) return "marker expected";
+        const int m = f[i + 1];
+        if (m == 0xFF) {  // fill byte
+            ++i;
+            continue;
+        }
+        const size_t len = ((size_t)f[i + 2] << 8) | f[i + 3];
+        if (len < 2 || i + 2 + len > n) return "marker segment runs past the file";
+        const uint8_t* p = f + i + 4;
+        const size_t body = len - 2;
+        if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
+            // APPn / COM
+        } else if (m == 0xDB) {
+            for (size_t o = 0; o < body; o += 65) {
+                if (o + 65 > body) return "malformed DQT";
+                if (p[o] >> 4) return "16-bit quantisation table";
+                if ((p[o] & 15) > 3) return "malformed DQT";
+                for (int k = 0; k < 64; ++k) qt[p[o] & 15][k] = p[o + 1 + k];
+                have_qt[p[o] & 15] = true;
+            }
+        } else if (m == 0xC4) {
+            for (size_t o = 0; o < body;) {
+                if (o + 17 > body) return "malformed DHT";
+                const int tc = p[o] >> 4, th = p[o] & 15;
+                size_t cnt = 0;
+                for (int k = 0; k < 16; ++k) cnt += p[o + 1 + k];
+                if (o + 17 + cnt > body) return "malformed DHT";
+                if (tc > 1 || th > 1) return "Huffman table id outside 0..1";
+                const uint8_t* bits = tc ? kAcBits[th] : kDcBits[th];
+                const uint8_t* vals = tc ? kAcVals[th] : kDcVals;
+                if (cnt != (tc ? 162u : 12u)) return "Huffman tables other than Annex K (optimised coding)";
+                for (int k = 0; k < 16; ++k)
+                    if (p[o + 1 + k] != bits[k]) return "Huffman tables other than Annex K (optimised coding)";
+                for (size_t k = 0; k < cnt; ++k)
+                    if (p[o + 17 + k] != vals[k]) return "Huffman tables other than Annex K (optimised coding)";
+                have_ht[tc][th] = true;
+                o += 17 + cnt;
+            }
+        } else if (m == 0xC0) {
+            if (sof) return "two frame headers";
+            if (body < 6) return "malformed SOF0";
+            if (p[0] != 8) return "sample precision other than 8 bits";
+            info->H = (p[1] << 8) | p[2];
+            info->W = (p[3] << 8) | p[4];
+            if (p[5] != 3) return "not three components (grey or CMYK)";
+            if (body != 15) return "malformed SOF0";
+            for (int c = 0; c < 3; ++c) {
+                ids[c] = p[6 + 3 * c];
+                if (p[7 + 3 * c] != (c ? 0x11 : 0x21)) return "chroma subsampling other than 4:2:2 (2x1, 1x1, 1x1)";
+                tq[c] = p[8 + 3 * c];
+                if (tq[c] > 3) return "malformed SOF0";
+            }
+            if (info->H <= 0 || info->W <= 0 || info->H % 8 || info->W % 16)
+                return "size is not whole MCUs (H % 8 == 0, W % 16 == 0)";
+            sof = true;
+        } else if (m >= 0xC1 && m <= 0xCF && m != 0xC8) {
+            return m == 0xC2 ? "progressive file" : "not a baseline (SOF0) file";
+        } else if (m == 0xDD) {
+            if (body != 2) return "malformed DRI";
+            if (p[0] || p[1]) return "restart interval";
+        } else if (m == 0xDA) {
+            if (!sof) return "scan before the frame header";
+            if (body < 1 || p[0] != 3) return "not one interleaved scan of three components";
+            if (body != 10) return "malformed SOS";
+            for (int c = 0; c < 3; ++c) {
+                if (p[1 + 2 * c] != ids[c]) return "scan components out of frame order";
+                if (p[2 + 2 * c] != (c ? 0x11 : 0x00)) return "Huffman table selectors other than 0/0, 1/1, 1/1";
+            }
+            if (p[7] != 0 || p[8] != 63 || p[9] != 0) return "not a sequential scan (Ss = 0, Se = 63, Ah = Al = 0)";
+            if (!(have_ht[0][0] && have_ht[0][1] && have_ht[1][0] && have_ht[1][1])) return "missing Huffman table";
+            if (!(have_qt[tq[0]] && have_qt[tq[1]] && have_qt[tq[2]])) return "missing quantisation table";
+            for (int k = 0; k < 64; ++k)
+                if (qt[tq[1]][k] != qt[tq[2]][k]) return "Cb and Cr use different quantisation tables";
+            for (int k = 0; k < 64; ++k) {
+                info->qtab[0][k] = qt[tq[0]][k];
+                info->qtab[1][k] = qt[tq[1]][k];
+                if (!qt[tq[0]][k] || !qt[tq[1]][k]) return "zero quantisation step";
+            }
+            info->scan_off = (long long)(i + 2 + len);
+            if (n < (size_t)info->scan_off + 2 || f[n - 2] != 0xFF || f[n - 1] != 0xD9) return "no EOI at the end of the file";
+            info->scan_len = (long long)n - 2 - info->scan_off;
+            return nullptr;
+        } else {
+            return "unexpected marker before the scan";
+        }
+        i += 2 + len;
+    }
+}
+
+inline int unstuffed_capacity(long long scan_capacity) { return (int)((scan_capacity + 8 + 255) & ~255LL); }
+
+// The host twin of the device decoder for one image: the same unstuffing rule, symbol step, rounds, write pass, DC
+// scan and IDCT, with a plain loop over subsequences where the kernel has threads.  scan = the raw entropy segment.
+// Returns the status (0 = valid); decoded planar [3][H][W] (zeros when the status is not 0).
+inline int decode_image_host(const uint8_t* scan, long long scan_len, long long capacity, const uint8_t qz[2][64],
+                             int H, int W, int sub_bits, float* decoded, int* rounds_out) {
+    static const DecTables T = make_dec_tables();
+    const int nb = blocks_per_image(H, W), cw = W / 2;
+    bool marker_error = false;
+    int extra = 0;
+    if (scan_len < 0) scan_len = 0;
+    if (scan_len > capacity) {
+        scan_len = capacity;
+        extra = kStTooLong;
+    }
+    std::vector<uint8_t> u;
+    u.reserve((size_t)scan_len);
+    for (long long k = 0; k < scan_len; ++k) {
+        const int prev = k ? scan[k - 1] : 0, cur = scan[k];
+        marker_error |= ff_error(prev, cur, k == scan_len - 1);
+        if (!ff_dropped(prev, cur)) u.push_back((uint8_t)cur);
+    }
+    const BitReader R{u.data(), (uint32_t)u.size()};
+    const uint32_t total_bits = (uint32_t)u.size() * 8u;
+    const int nsub = sub_count(total_bits, sub_bits);
+    std::vector<SubExit> a((size_t)nsub), b((size_t)nsub);
+    SubExit *cur = a.data(), *nxt = b.data();
+    for (int i = 0; i < nsub; ++i) cur[i] = sync_round0(T, R, i, sub_bits, total_bits);
+    int rounds = 0;
+    for (int r = 1; r < nsub; ++r) {
+        bool changed = false;
+        for (int i = 0; i < nsub; ++i) changed |= sync_round(T, R, i, sub_bits, total_bits, cur, nxt);
+        ++rounds;
+        std::swap(cur, nxt);
+        if (!changed) break;
+    }
+    if (rounds_out) *rounds_out = rounds;
+    std::vector<int16_t> coef((size_t)nb * 64);
+    int blocks = 0;
+    bool sym_error = false;
+    for (int i = 0; i < nsub; ++i) {
+        write_subsequence(T, R, i, sub_bits, total_bits, cur, blocks, coef.data(), nb);
+        blocks += (int)(cur[i].w >> 16);
+        sym_error |= (cur[i].w & kExitError) != 0;
+    }
+    const int status = extra | decode_status(R, total_bits, nsub, nsub ? cur[nsub - 1] : SubExit{0, 0}, blocks, nb,
+                                             sym_error, marker_error);
+    if (status) {
+        for (size_t k = 0; k < (size_t)3 * H * W; ++k) decoded[k] = 0.0f;
+        return status;
+    }
+    for (int comp = 0; comp < 3; ++comp) {
+        uint32_t dc = 0;
+        for (int s = 0; s < dc_blocks_of(comp, nb); ++s) {
+            int16_t& slot = coef[(size_t)dc_block_of(comp, s) * 64];
+            dc += (uint32_t)(int)slot;
+            slot = (int16_t)(uint16_t)dc;
+        }
+    }
+    uint16_t q[2][64];
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 64; ++k) q[c][kNatural[k]] = qz[c][k];
+    std::vector<uint8_t> yp((size_t)H * W), cp[2];
+    cp[0].resize((size_t)H * cw);
+    cp[1].resize((size_t)H * cw);
+    const int mw = W / 16;
+    int d[64];
+    for (int blk = 0; blk < nb; ++blk) {
+        const int m = blk >> 2, slot = blk & 3, mx = m % mw, my = m / mw;
+        const int comp = slot < 2 ? 0 : slot - 1, bx = slot < 2 ? 2 * mx + slot : mx;
+        coef_block_to_samples(coef.data() + (size_t)blk * 64, q[comp ? 1 : 0], d);
+        uint8_t* plane = comp ? cp[comp - 1].data() : yp.data();
+        const int pw = comp ? cw : W;
+        for (int r = 0; r < 8; ++r)
+            for (int c = 0; c < 8; ++c) plane[(size_t)(my * 8 + r) * pw + bx * 8 + c] = (uint8_t)d[r * 8 + c];
+    }
+    planes_to_pixels_host(yp.data(), cp[0].data(), cp[1].data(), H, W, decoded);
+    return 0;
 }
 
 }  // namespace jpeg

@@ -67,6 +67,12 @@ class WgradJob(ctypes.Structure):
                                     "reserved")]
 
 
+class JpegInfo(ctypes.Structure):
+    """hyres_jpeg_info: what hyres_jpeg_parse reads from a file's marker segments (include/hyres_hip.h)."""
+    _fields_ = [("supported", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("scan_off", ctypes.c_longlong), ("scan_len", ctypes.c_longlong), ("qtab", ctypes.c_ubyte * 128)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _LL = ctypes.c_longlong
@@ -157,6 +163,10 @@ _SIGS = {
     "hyres_jpeg_stream_bytes": (_LL, [_I, _I]),
     "hyres_jpeg_roundtrip": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P]),
     "hyres_jpeg_roundtrip_host": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P]),
+    "hyres_jpeg_parse": (_I, [_P, _LL, ctypes.POINTER(JpegInfo)]),
+    "hyres_jpeg_decode_workspace_bytes": (_LL, [_I, _I, _I, _LL]),
+    "hyres_jpeg_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _LL, _P]),
+    "hyres_jpeg_decode_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _LL, _P]),
     "hyres_msssim_workspace_bytes": (_LL, [_I, _I, _I, _I, _I]),
     "hyres_msssim": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),
     "hyres_msssim_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),

@@ -15,8 +15,12 @@ multi-GPU scaling story.
 
 Opt-in device codec: ``device_codec=True`` (or HYRES_JPEG_CODEC=device) runs the round trip of a supported GPU
 tensor (3-channel fp32, H % 8 == 0, W % 16 == 0) as HIP kernels (hyres_hip/jpeg_device.py), bit-exact with the
-host path: no device-to-host copy, no second upload, ``jpeg_bpp`` a 0-dim device tensor.  Everything else (CPU
-tensors, grey input, ragged sizes, ``decompress`` of foreign bytes) keeps the host path; the default is ``host``.
+host path: no device-to-host copy, no second upload, ``jpeg_bpp`` a 0-dim device tensor.  With it ``decompress`` of
+baseline 4:2:2 files (Annex K Huffman tables, one interleaved scan, no restart interval, whole MCUs, one common size,
+a GPU target) decodes on the device as well (``jpeg_device.decode``: a self-synchronising parallel Huffman decoder,
+bit-exact with libjpeg-turbo); the host reads the file headers only.  Everything else (CPU tensors or targets, grey
+input, ragged sizes, progressive / 4:2:0 / 4:4:4 / optimised-table / restart-marker files, batches of mixed sizes)
+keeps the host path; the default is ``host``.
 """
 from __future__ import annotations
 
@@ -114,7 +118,24 @@ class TurboJPEGCompression(nn.Module):
         datas = self._map(lambda im: self.jpeg.encode(im, quality=self.quality), list(imgs))
         return [io.BytesIO(d) for d in datas]
 
+    def decode_on_device(self, datas, device) -> bool:
+        """These files take the device decoder: the device codec is on, the target is a GPU and every file is a
+        supported 4:2:2 baseline file of one common size (else the host path, unchanged)."""
+        if not (self.device_codec and datas and torch.device(device).type == "cuda"):
+            return False
+        sizes = set()
+        for d in datas:
+            info = jpeg_device._parse(d)[0]
+            if info is None:
+                return False
+            sizes.add((info.H, info.W))
+        return len(sizes) == 1
+
     def decompress(self, compressed_buffers, device) -> torch.Tensor:
+        if self.device_codec:
+            datas = [b.getvalue() for b in compressed_buffers]
+            if self.decode_on_device(datas, device):
+                return jpeg_device.decode(datas, device)  # the host reads the file headers only
         arrs = self._map(lambda b: self.jpeg.decode(b.getvalue()), list(compressed_buffers))
         return self._stack(arrs).to(device)
 

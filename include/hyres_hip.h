@@ -713,6 +713,44 @@ int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, 
                               unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
                               hyres_stream_t s);
 
+/* Decoding foreign 4:2:2 files on the device: a self-synchronising parallel Huffman decoder (csrc/jpeg_core.h),
+ * bit-exact with libjpeg-turbo's decode. */
+typedef struct hyres_jpeg_info {
+    int supported;          /* 1: the device decoder takes the file */
+    int H, W;               /* valid when supported */
+    long long scan_off;     /* the entropy-coded segment inside the file: after the SOS header ... */
+    long long scan_len;     /* ... up to the trailing EOI */
+    unsigned char qtab[128]; /* luminance then chrominance quantiser, zigzag order (the DQT payloads) */
+} hyres_jpeg_info;
+/* Parses the marker segments of a JPEG file (host). supported = baseline SOF0, 8-bit, three components sampled
+ * 2x1 / 1x1 / 1x1 in one interleaved scan (Ss = 0, Se = 63, Ah = Al = 0), no restart interval, 8-bit DQT tables of
+ * any values, the four Annex K Huffman tables, H % 8 == 0 and W % 16 == 0; APPn / COM segments anywhere. Returns
+ * HYRES_OK for every readable argument; when supported == 0, hyres_last_error_string() gives the reason. */
+int hyres_jpeg_parse(const unsigned char* file, long long nbytes, hyres_jpeg_info* info);
+/* workspace of hyres_jpeg_decode for B files of H x W whose entropy segments take at most scan_capacity bytes each
+ * (1 <= scan_capacity < 2^28), valid for every sub_bits, or -1 (host) */
+long long hyres_jpeg_decode_workspace_bytes(int B, int H, int W, long long scan_capacity);
+/* Decodes B files of one size. scans: the raw (still stuffed) entropy segments, image b's at scans + scan_off[b],
+ * scan_len[b] <= scan_capacity bytes; qtabs [B][2][64]: the files' quantisers in zigzag order; sub_bits: bits per
+ * subsequence, a multiple of 32 in 32 .. 8192, 0 = the default; block_threads: threads of the work-group that
+ * decodes one image, a multiple of 64 in 64 .. 1024, 0 = the default. decoded [B,3,H,W] fp32 = byte / 255 (channel
+ * 0 = B); status[b] = 0 for a valid file, else bits 1 marker inside the segment, 2 invalid code or run past index
+ * 63, 4 block count, 8 end position or padding, 16 segment longer than scan_capacity — the image's output is then
+ * unspecified, every access stays inside the workspace; rounds (may be NULL): rounds[b] = sync rounds run, at
+ * most the number of subsequences - 1. All device pointers; seven launches on ``s`` whose grids depend on
+ * (B, H, W, scan_capacity, block_threads) alone — no host sync, allocation or copy: capture-legal. */
+int hyres_jpeg_decode(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                      const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                      int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                      hyres_stream_t s);
+/* the host twin: the same symbol step, rounds, write pass, DC scan and IDCT (csrc/jpeg_core.h) on host memory, a
+ * plain loop over subsequences where the kernel has threads; decoded is zero-filled where status[b] != 0;
+ * block_threads, ws and s are ignored, no GPU call is made (host) */
+int hyres_jpeg_decode_host(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                           const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                           int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                           hyres_stream_t s);
+
 /* ------------------------------------------------------------------------------------------ */
 /* MS-SSIM / SSIM metric: pytorch_msssim's ms_ssim at its defaults (11-tap sigma-1.5 window, valid filtering,     */
 /* K = (0.01, 0.03), 2x2 average pooling with padding side % 2 between levels)                                   */

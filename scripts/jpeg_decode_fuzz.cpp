@@ -1,0 +1,93 @@
+// Bounds check of the JPEG file decoder's shared host/device code (csrc/jpeg_core.h) on corrupt input, for a host
+// sanitizer build.  No GPU, no library: the header is all it needs.
+//
+//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -I hyres-residual-enhanced-hybrid-image-compression_amd/csrc scripts/jpeg_decode_fuzz.cpp -o jpeg_decode_fuzz
+//   ./jpeg_decode_fuzz
+//
+// It writes files with roundtrip_image_host at three sizes and four qualities, checks that each decodes back to the
+// round trip's own pixels, and then decodes every file after deterministic mutations (truncation at 64 evenly
+// spaced lengths, with and without a trailing EOI, and 256 single-bit flips chosen by an LCG) at sub_bits 32 and the
+// default.  A mutated file may decode or be refused; it must not touch memory outside its buffers.  Prints the
+// number of decodes and exits 0.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "jpeg_core.h"
+
+using namespace hyres::jpeg;
+
+static uint32_t lcg(uint32_t& s) { return s = s * 1664525u + 1013904223u; }
+
+struct Counts {
+    long parsed = 0, refused = 0, decoded_ok = 0, decoded_bad = 0;
+};
+
+// parse + decode one file exactly as the library's host twin does; returns the status or -1 when the parser refuses
+static int decode_file(const std::vector<uint8_t>& f, int sub_bits, std::vector<float>& out, Counts& n) {
+    FileInfo fi{};
+    if (parse_file(f.data(), f.size(), &fi)) {
+        ++n.refused;
+        return -1;
+    }
+    ++n.parsed;
+    out.assign((size_t)3 * fi.H * fi.W, -1.0f);
+    int rounds = -1;
+    const long long cap = fi.scan_len > 0 ? fi.scan_len : 1;
+    const int st = decode_image_host(f.data() + fi.scan_off, fi.scan_len, cap, fi.qtab, fi.H, fi.W, sub_bits,
+                                     out.data(), &rounds);
+    const int nsub = sub_count((uint32_t)fi.scan_len * 8u, sub_bits);
+    if (rounds < 0 || rounds > (nsub > 0 ? nsub : 1)) {
+        std::printf("rounds %d outside 0 .. %d\n", rounds, nsub);
+        std::exit(1);
+    }
+    ++(st ? n.decoded_bad : n.decoded_ok);
+    return st;
+}
+
+int main() {
+    const int sizes[3][2] = {{8, 16}, {24, 48}, {64, 128}};
+    const int qualities[4] = {1, 25, 50, 95};
+    const int subs[2] = {32, kDefaultSubBits};
+    Counts n;
+    uint32_t seed = 12345u;
+    std::vector<float> out;
+    for (const auto& hw : sizes)
+        for (int q : qualities) {
+            const int H = hw[0], W = hw[1];
+            std::vector<float> x((size_t)3 * H * W), dec(x.size());
+            for (size_t i = 0; i < x.size(); ++i) {  // noise over a ramp: long and short code words, some 0xFF bytes
+                const float ramp = (float)(i % (size_t)W) / (float)W;
+                x[i] = 0.5f * ramp + 0.5f * (float)(lcg(seed) >> 24) / 255.0f;
+            }
+            std::vector<uint8_t> file;
+            roundtrip_image_host(x.data(), H, W, q, dec.data(), &file);
+            for (int sb : subs) {
+                if (decode_file(file, sb, out, n) != 0 || std::memcmp(out.data(), dec.data(), dec.size() * 4)) {
+                    std::printf("%dx%d q%d sub_bits %d: the unmutated file does not decode to the round trip\n", H, W,
+                                q, sb);
+                    return 1;
+                }
+                for (int t = 0; t < 64; ++t) {  // truncation, as it is and closed with an EOI
+                    const size_t len = file.size() * (size_t)t / 64;
+                    std::vector<uint8_t> cut(file.begin(), file.begin() + (long)len);
+                    decode_file(cut, sb, out, n);
+                    cut.push_back(0xFF);
+                    cut.push_back(0xD9);
+                    decode_file(cut, sb, out, n);
+                }
+                uint32_t s = 99u + (uint32_t)(H * 131 + q);
+                for (int t = 0; t < 256; ++t) {  // one flipped bit anywhere after the SOI
+                    std::vector<uint8_t> m = file;
+                    const size_t bit = 16 + (size_t)(lcg(s) >> 4) % ((file.size() - 2) * 8);
+                    m[bit >> 3] ^= (uint8_t)(0x80u >> (bit & 7));
+                    decode_file(m, sb, out, n);
+                }
+            }
+        }
+    std::printf("files handled %ld: refused by the parser %ld, decoded %ld (valid %ld, status != 0 %ld)\n",
+                n.parsed + n.refused, n.refused, n.parsed, n.decoded_ok, n.decoded_bad);
+    return 0;
+}
