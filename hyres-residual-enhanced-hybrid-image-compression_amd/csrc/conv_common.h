@@ -1,5 +1,5 @@
-// Internal declarations shared by the convolution (conv.hip, ru_fused.hip through halo_common.h) and weight-gradient
-// (wgrad.hip) units.
+// Internal declarations shared by the convolution (conv.hip, conv_stream.hip through stream_common.h, ru_fused.hip
+// through halo_common.h) and weight-gradient (wgrad.hip) units.
 #pragma once
 #include "common.h"
 
@@ -42,6 +42,10 @@ __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ half4_t bload4h(__amdgpu_buffer_rsrc_t r, int off) {
+    return __builtin_bit_cast(half4_t, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
+}
+__device__ __forceinline__ float4 h2f4(half4_t h) { return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w); }
 
 typedef _Float16 halfx4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 halfx8_t __attribute__((ext_vector_type(8)));
@@ -82,5 +86,56 @@ __device__ __forceinline__ void bf6_put3(__bf16* base, int o, const float4& v) {
     *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
     *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
 }
+
+// ---- the forward convolution kernels' argument block (conv.hip, conv_stream.hip)
+struct ConvArgs {
+    hyres_conv_geom g;
+    const float* x;
+    const float* w2;
+    int ldw;
+    float* y;
+    hyres_epilogue e;
+    int M;       // B*Hq*Wq
+    int nsplit;  // split-K factor (1 = fused epilogue)
+    int cps;     // K chunks per split
+    float* slab; // [nsplit][nphase][M][Co] partials when nsplit > 1
+    int vec4;    // every epilogue operand 16B aligned with ld % 4 == 0 and Co % 4 == 0
+    int w_bytes; // bytes of W2 (buffer-resource range)
+    int xcd;     // 1: grid.x = M tiles x N tiles in XCD-aware order (grid.y = 1)
+    int prio;    // 1: raise the wave priority while it issues its MFMA cluster (s_setprio)
+    int x_bytes; // conv1x1_stream_kernel: bytes of X (buffer-resource range)
+    int rsrc_ok; // every epilogue operand / output spans < 2 GB: the epilogues may address them by buffer resources
+    int b6sw;    // bf16x6 implicit GEMM: 64-B LDS rows with the 16-B slot XOR-swizzled by row bits 2..3 (round 6,
+                 // hyres_conv_tuning key 19, default 1) instead of 80-B padded rows
+};
+
+// a streaming kernel's instantiation as route() carries it: NT, KC or KS, the epilogue-operand bits F
+inline int pack_cfg(int nt, int k, int f) { return nt | (k << 4) | (f << 12); }
+inline int cfg_nt(int cfg) { return cfg & 15; }
+inline int cfg_k(int cfg) { return (cfg >> 4) & 255; }
+inline int cfg_f(int cfg) { return cfg >> 12; }
+
+inline long long gemm_rows(const hyres_conv_geom* g) { return (long long)g->B * g->Hq * g->Wq; }
+
+// single-tap, stride-1, same-size 1x1: the streaming kernels' geometry
+inline bool pointwise_same_size(const hyres_conv_geom* g) {
+    return g->nphase == 1 && g->ntaps == 1 && g->ish == 1 && g->isw == 1 && g->dh[0] == 0 && g->dw[0] == 0 &&
+           g->Hi == g->Hq && g->Wi == g->Wq && g->Ho == g->Hq && g->Wo == g->Wq;
+}
+
+// the PReLU-mask epilogues leave one slope-gradient partial per block: summed in a fixed order and added to dst (conv.hip)
+int prelu_slope_sum(const void* partials, int n, const void* dst, hipStream_t st);
+
+// ---- the streaming 1x1 family (conv_stream.hip) as route() and hyres_conv_forward (conv.hip) see it: eligibility
+// (pack_cfg(NT, KC or KS, F), or 0) and launch of the instantiation a cfg names
+int stream_cfg(const hyres_conv_geom* g, const hyres_epilogue* e);
+int stream_h_cfg(const hyres_conv_geom* g, const hyres_epilogue* e);
+int stream_hf_cfg(const hyres_conv_geom* g, const hyres_epilogue* e);
+int stream_b6_cfg(const hyres_conv_geom* g, const hyres_epilogue* e);
+bool stream_b6_ce();
+int launch_stream(const ConvArgs& a, int cfg, hipStream_t st);
+int launch_stream_h(const ConvArgs& a, int cfg, hipStream_t st);
+int launch_stream_hf(const ConvArgs& a, int cfg, hipStream_t st);
+int launch_stream_b6(const ConvArgs& a, int cfg, hipStream_t st);
 
 }  // namespace hyres

@@ -5,6 +5,7 @@ wrong values while its allocation (224 VGPRs x 2 waves per SIMD) left a 64-regis
 the whole file. These tests keep that guard from silently disappearing (a compiler update or an edit of the kernel's
 asm line) and list every persistent 512-thread kernel whose allocation still leaves room for another kernel's waves.
 """
+import json
 import os
 import sys
 
@@ -141,3 +142,16 @@ def test_stream_b6_kernels_fill_the_vgpr_file(meta):
     for k in ks:
         full = 512 if ("kernelILi6E" in k["name"] or "ELi12E" in k["name"] or "kernelILi4ELi8E" in k["name"]) else 256
         assert k["alloc"] == full and kernel_meta.residency(k)["hole_vgprs"] == 0 and k["scratch"] == 0, k
+
+
+def test_stream_kernels_instantiations_and_lds(meta):
+    """The per-wave streaming 1x1 kernels (csrc/conv_stream.hip, shared device code in csrc/stream_common.h): the set of
+    conv1x1_stream*_kernel instantiations and each one's LDS bytes are those of the build before the family's device
+    code was shared (tests/golden/stream_kernels.json, written from that build: independent of register allocation)."""
+    with open(os.path.join(HERE, "golden", "stream_kernels.json")) as f:
+        want = json.load(f)
+    ks = _find(meta, "conv1x1_stream")
+    names = kernel_meta.demangle([k["name"] for k in ks])
+    got = {n.replace("hyres::", "").replace("void ", "").split("(")[0]: k["lds"] for k, n in zip(ks, names)}
+    assert len(got) == len(ks)
+    assert got == want, {n: (want.get(n), got.get(n)) for n in set(want) | set(got) if want.get(n) != got.get(n)}

@@ -1,4 +1,4 @@
-"""conv1x1_stream_b6_kernel (csrc/conv.hip, round 5): the fp32 1x1 convs of the ResidualUnits / RBBs and their
+"""conv1x1_stream_b6_kernel (csrc/conv_stream.hip, round 5): the fp32 1x1 convs of the ResidualUnits / RBBs and their
 input-gradients (models/layers/attention.py:11-30, compressai ResidualBottleneckBlock at models/checkerboard.py:38-56)
 on a per-wave streaming kernel with bf16x6 products, every epilogue operand issued a co tile ahead.
 

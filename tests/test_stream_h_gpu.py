@@ -1,4 +1,4 @@
-"""The fp16-activation streaming 1x1 conv (csrc/conv.hip conv1x1_stream_h_kernel: io_f16 = 3, Ci / Co in {64, 96, 128},
+"""The fp16-activation streaming 1x1 conv (csrc/conv_stream.hip conv1x1_stream_h_kernel: io_f16 = 3, Ci / Co in {64, 96, 128},
 >= 16384 pixels, no streamed epilogue operand) and, for the layers WITH one (residual, ReLU mask, old y),
 conv1x1_stream_hf_kernel (round 6: operands a co tile ahead, row-shaped epilogue through LDS), which must equal the
 f16 tiles it replaces bit for bit (hyres_conv_tuning key 17 = 0 routes them back). Against torch float64 on the same fp16 values (X fp16, W rounded to fp16, fp32 bias, fp16 residual / mask /
