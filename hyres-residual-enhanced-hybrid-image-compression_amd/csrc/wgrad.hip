@@ -2374,17 +2374,18 @@ static int wgrad_issue(const hyres_wgrad_desc* d0, const float* pp, const float*
                            dim3(256), 0, st, (const _Float16*)x, ld, wsf + off, P, C);
         x = wsf + off;
     };
+    // refusals first: nothing, the fp32 copies included, is written for a launch that is refused
+    const bool vec = r.vp && r.vq;
+    HY_REQUIRE(!r.sqr || vec, HYRES_E_SHAPE, "wgrad: square_q needs the vector path");
+    // the plan (chunk size, split count, workspace) assumed the f16 kernel: its operands must be aligned
+    HY_REQUIRE(!r.f16 || vec, HYRES_E_ALIGN, "wgrad(f16): P/Q must be 16-byte aligned");
+    HY_REQUIRE(!r.halo || vec, HYRES_E_ALIGN, "wgrad(halo): P/Q must be 16-byte aligned");
     if (r.cvt & 1) to_f32(pp, r.swap ? d0->ldq : d0->ldp, (long long)d->B * d->Hq * d->Wq, d->M, r.cvtp_off);
     if (r.cvt & 2) to_f32(qq, r.swap ? d0->ldp : d0->ldq, (long long)d->B * d->Hqq * d->Wqq, d->N, r.cvtq_off);
     if (r.cvt) {
         int rc0 = HY_LAUNCH_CHECK("half_to_float_2d");
         if (rc0) return rc0;
     }
-    const bool vec = r.vp && r.vq;
-    HY_REQUIRE(!r.sqr || vec, HYRES_E_SHAPE, "wgrad: square_q needs the vector path");
-    // the plan (chunk size, split count, workspace) assumed the f16 kernel: its operands must be aligned
-    HY_REQUIRE(!r.f16 || vec, HYRES_E_ALIGN, "wgrad(f16): P/Q must be 16-byte aligned");
-    HY_REQUIRE(!r.halo || vec, HYRES_E_ALIGN, "wgrad(halo): P/Q must be 16-byte aligned");
     WgradArgs a;
     a.d = *d; a.p = pp; a.q = qq; a.slab = wsf; a.chunks_per_split = r.cps; a.nchunks = r.nchunks;
     a.mtiles = r.mtiles; a.ntiles = r.ntiles; a.ngroups = r.ngroups; a.nblocks = r.nblocks; a.tapn = r.tapn;
@@ -2465,9 +2466,9 @@ static int wgrad_issue(const hyres_wgrad_desc* d0, const float* pp, const float*
     return 0;
 }
 
-int hyres_wgrad_kernel_name(const hyres_wgrad_desc* d, char* buf, int n) {
+static int wgrad_name(const hyres_wgrad_desc* d, const WgradFacts& f, char* buf, int n) {
     HY_REQUIRE(d && buf && n > 0, HYRES_E_ARG, "wgrad_kernel_name: bad args");
-    const WgradRoute r = wgrad_route(d, WgradFacts::ideal());
+    const WgradRoute r = wgrad_route(d, f);
     auto tf = [](bool b) { return b ? "true" : "false"; };
     char tile[32];
     snprintf(tile, sizeof tile, "%d, %d, %d, %d", r.TM, r.TN, r.WM, r.WN);
@@ -2500,6 +2501,15 @@ int hyres_wgrad_kernel_name(const hyres_wgrad_desc* d, char* buf, int n) {
             break;
     }
     return 0;
+}
+
+int hyres_wgrad_kernel_name(const hyres_wgrad_desc* d, char* buf, int n) {
+    return wgrad_name(d, WgradFacts::ideal(), buf, n);
+}
+
+int hyres_wgrad_kernel_name_at(const hyres_wgrad_desc* d, int p_aligned, int q_aligned, int ws_aligned, char* buf,
+                               int n) {
+    return wgrad_name(d, WgradFacts{p_aligned != 0, q_aligned != 0, ws_aligned != 0}, buf, n);
 }
 
 int hyres_wgrad_plan(const hyres_wgrad_desc* d, int* nsplit, int* blocks, int* threads, int* lanes) {

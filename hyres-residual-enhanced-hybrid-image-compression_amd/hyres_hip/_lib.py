@@ -105,6 +105,7 @@ _SIGS = {
     "hyres_wgrad_desc_deconv2d": (_I, [ctypes.POINTER(WgradDesc)] + [_I] * 9),
     "hyres_wgrad_workspace_bytes": (_LL, [ctypes.POINTER(WgradDesc)]),
     "hyres_wgrad_kernel_name": (_I, [ctypes.POINTER(WgradDesc), ctypes.c_char_p, _I]),
+    "hyres_wgrad_kernel_name_at": (_I, [ctypes.POINTER(WgradDesc), _I, _I, _I, ctypes.c_char_p, _I]),
     "hyres_wgrad_plan": (_I, [ctypes.POINTER(WgradDesc), _P, _P, _P, _P]),
     "hyres_conv_wgrad": (_I, [ctypes.POINTER(WgradDesc), _P, _P, _P, _P, _P, _LL, _P]),
     "hyres_conv_wgrad_deferred": (_I, [ctypes.POINTER(WgradDesc), _P, _P, _P, _P, _P, _LL, ctypes.POINTER(WgradJob),

@@ -256,6 +256,11 @@ long long hyres_wgrad_workspace_bytes(const hyres_wgrad_desc* d);
  * e.g. "wgrad_halo_bf6_pf2_kernel<3, 1, 1, 2>" (16B-aligned operands and workspace assumed).  Host-only, no
  * launch: the launcher's own choice function. */
 int hyres_wgrad_kernel_name(const hyres_wgrad_desc* d, char* buf, int n);
+/* The same for a launch whose P / Q / workspace pointers are (non-zero) or are not (0) 16-byte aligned: a misaligned
+ * operand reroutes the 1x1 and thin kernels to wgrad_kernel and clears its float4 flags.  Where hyres_conv_wgrad
+ * refuses the launch (a halo / f16 descriptor off the vector path) the name is that of the planned kernel. */
+int hyres_wgrad_kernel_name_at(const hyres_wgrad_desc* d, int p_aligned, int q_aligned, int ws_aligned, char* buf,
+                               int n);
 /* The launcher's plan for d under the same assumption: the split count, the grid (blocks, rounded up to a multiple
  * of 8; the thin kernel's row blocks x tap groups as they are), the block size and the lanes of the split reduce.
  * Any output may be NULL.  Pure host function. */
