@@ -3,8 +3,9 @@
 //
 //   jpeg_blocks_kernel    one thread per 8x8 block: pixels -> bytes -> Y / downsampled Cb / Cr -> forward DCT ->
 //                         quantise -> int16 zigzag coefficients [B][blocks][64] (scan order), and in the same pass
-//                         dequantise -> inverse DCT -> u8 Y / Cb / Cr planes
-//   jpeg_decode_kernel    fancy h2v1 upsample + YCbCr -> BGR + /255 into the fp32 NCHW output
+//                         dequantise -> inverse DCT -> u8 Y / Cb / Cr planes of the padded extents; blocks that reach
+//                         past the image gather with clamped coordinates, a dummy block repeats its neighbour's DC
+//   jpeg_decode_kernel    fancy h2v1 upsample + YCbCr -> BGR + /255 into the fp32 NCHW output of the true extents
 //   jpeg_count_kernel     Huffman bit count per block (DC predicted from the previous block of the component)
 //   jpeg_scan_kernel      exclusive scan of the bit counts per image -> every block's bit offset
 //   jpeg_pack_kernel      each block's code words at its offset into a big-endian word buffer that
@@ -48,9 +49,10 @@ static Layout make_layout(int B, int H, int W) {
     L.nwords = L.nchunks * kChunkWords;
     long long o = 0;
     L.coef = o, o = align256(o + (long long)B * L.nb * 64 * 2);
-    L.yp = o, o = align256(o + (long long)B * H * W);
-    L.cbp = o, o = align256(o + (long long)B * H * (W / 2));
-    L.crp = o, o = align256(o + (long long)B * H * (W / 2));
+    const long long pix = (long long)B * padded_h(H) * padded_w(W);  // the planes have the padded extents
+    L.yp = o, o = align256(o + pix);
+    L.cbp = o, o = align256(o + pix / 2);
+    L.crp = o, o = align256(o + pix / 2);
     L.bits = o, o = align256(o + (long long)B * L.nb * 4);
     L.total = o, o = align256(o + (long long)B * 4);
     L.words = o, o = align256(o + (long long)B * L.nwords * 4);
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_blocks_kernel(const float* __re
     __shared__ uint16_t q[128];
     if (threadIdx.x < 128) q[threadIdx.x] = Q.q[threadIdx.x >> 6][threadIdx.x & 63];
     __syncthreads();
-    const int mw = W / 16, nmcu = mw * (H / 8), nb = 4 * nmcu;
+    const int mw = mcus_per_row(W), nmcu = mw * block_rows(H), nb = 4 * nmcu;
     const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (gid >= (long long)B * nb) return;
     const int b = (int)(gid / nb), i = (int)(gid % nb);
@@ -109,13 +111,11 @@ __global__ __launch_bounds__(kThreads) void jpeg_blocks_kernel(const float* __re
     }
     const uint16_t* qt = q + (comp ? 64 : 0);
     int d[64];
-    sample_block(x + (long long)b * 3 * H * W, H, W, comp, bx, by, d);
-    fdct_islow(d);
-    quantize(d, qt);
+    encode_block_coefs(x + (long long)b * 3 * H * W, H, W, comp, bx, by, qt, d);
     store_zigzag(coef + ((long long)b * nb + blk) * 64, d, std::make_index_sequence<32>());
     dequant_idct(d, qt);
-    const int pw = comp ? W / 2 : W;
-    uint8_t* plane = (comp == 0 ? yp : (comp == 1 ? cbp : crp)) + (long long)b * H * pw;
+    const int pw = comp ? mw * 8 : mw * 16;
+    uint8_t* plane = (comp == 0 ? yp : (comp == 1 ? cbp : crp)) + (long long)b * block_rows(H) * 8 * pw;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         uint32_t u[8];  // samples in 0..255
@@ -127,33 +127,43 @@ __global__ __launch_bounds__(kThreads) void jpeg_blocks_kernel(const float* __re
     }
 }
 
-// one thread per chroma sample: output columns 2i and 2i+1 of the three planes (plane 0 = B)
+// one thread per real chroma sample (ceil(W/2) a row): output columns 2i and 2i+1 of the three planes (plane 0 = B).
+// The u8 planes have the padded extents ph x pw (= H x W for whole MCUs); column 2i+1 == W of an odd W is dropped.
 __global__ __launch_bounds__(kThreads) void jpeg_decode_kernel(const uint8_t* __restrict__ yp,
                                                               const uint8_t* __restrict__ cbp,
                                                               const uint8_t* __restrict__ crp, int B, int H, int W,
-                                                              float* __restrict__ out) {
-    const int cw = W / 2;
+                                                              int ph, int pw, float* __restrict__ out) {
+    const int cw = (W + 1) / 2, pcw = pw / 2;
     const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (gid >= (long long)B * H * cw) return;
     const int i = (int)(gid % cw);
     const long long row = gid / cw;  // b * H + r
     const int b = (int)(row / H), r = (int)(row % H);
+    const long long prow = (long long)b * ph + r;
     int cb[2], cr[2];
-    upsample_pair(cbp + row * cw, cw, i, cb[0], cb[1]);
-    upsample_pair(crp + row * cw, cw, i, cr[0], cr[1]);
+    upsample_pair(cbp + prow * pcw, cw, i, cb[0], cb[1]);
+    upsample_pair(crp + prow * pcw, cw, i, cr[0], cr[1]);
     float v[3][2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         int R, G, Bl;
-        ycc_to_rgb(yp[row * W + 2 * i + h], cb[h], cr[h], R, G, Bl);
+        ycc_to_rgb(yp[prow * pw + 2 * i + h], cb[h], cr[h], R, G, Bl);  // 2i + 1 <= pw - 1: inside the padded row
         v[0][h] = __fdiv_rn((float)Bl, 255.0f);  // a true fp32 division, not a reciprocal multiply
         v[1][h] = __fdiv_rn((float)G, 255.0f);
         v[2][h] = __fdiv_rn((float)R, 255.0f);
     }
     const long long plane = (long long)H * W;
     float* o = out + (long long)b * 3 * plane + (long long)r * W + 2 * i;
+    if (!(W & 1)) {  // uniform: every pair is whole and 8-byte aligned
 #pragma unroll
-    for (int c = 0; c < 3; ++c) *reinterpret_cast<float2*>(o + c * plane) = make_float2(v[c][0], v[c][1]);
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<float2*>(o + c * plane) = make_float2(v[c][0], v[c][1]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            o[c * plane] = v[c][0];
+            if (2 * i + 1 < W) o[c * plane + 1] = v[c][1];
+        }
+    }
 }
 
 __device__ __forceinline__ int pred_dc(const int16_t* coef_img, int blk) {
@@ -352,9 +362,10 @@ static DecLayout make_dec_layout(int B, int H, int W, long long capacity) {
     L.exits = o, o = align256(o + (long long)B * 2 * L.maxsub * (long long)sizeof(SubExit));
     L.first = o, o = align256(o + (long long)B * L.maxsub * 4);
     L.coef = o, o = align256(o + (long long)B * L.nb * 64 * 2);
-    L.yp = o, o = align256(o + (long long)B * H * W);
-    L.cbp = o, o = align256(o + (long long)B * H * (W / 2));
-    L.crp = o, o = align256(o + (long long)B * H * (W / 2));
+    const long long pix = (long long)B * padded_h(H) * padded_w(W);
+    L.yp = o, o = align256(o + pix);
+    L.cbp = o, o = align256(o + pix / 2);
+    L.crp = o, o = align256(o + pix / 2);
     L.end = o;
     return L;
 }
@@ -557,7 +568,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const int16_t* __re
     if (threadIdx.x < 128)
         q[(threadIdx.x & 64) + kNatural[threadIdx.x & 63]] = qtabs[(long long)b * 128 + threadIdx.x];
     __syncthreads();
-    const int mw = W / 16, nmcu = mw * (H / 8), nb = 4 * nmcu;
+    const int mw = mcus_per_row(W), nmcu = mw * block_rows(H), nb = 4 * nmcu;
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= nb) return;
     int comp, bx, by, blk;
@@ -584,8 +595,8 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const int16_t* __re
     }
     int d[64];
     coef_block_to_samples(zz, q + (comp ? 64 : 0), d);
-    const int pw = comp ? W / 2 : W;
-    uint8_t* plane = (comp == 0 ? yp : (comp == 1 ? cbp : crp)) + (long long)b * H * pw;
+    const int pw = comp ? mw * 8 : mw * 16;
+    uint8_t* plane = (comp == 0 ? yp : (comp == 1 ? cbp : crp)) + (long long)b * block_rows(H) * 8 * pw;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         uint32_t u[8];  // samples in 0..255
@@ -597,10 +608,16 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const int16_t* __re
     }
 }
 
-static int check_shape(const char* what, int B, int H, int W) {
-    HY_REQUIRE(B >= 1 && H >= 8 && W >= 16 && H % 8 == 0 && W % 16 == 0 && H <= 65528 && W <= 65520, HYRES_E_SHAPE,
-               "%s: B >= 1, H %% 8 == 0, W %% 16 == 0, H, W < 65536 (got %d x %d x %d)", what, B, H, W);
-    HY_REQUIRE((long long)blocks_per_image(H, W) * kMaxBlockBits < (1LL << 31) && (long long)B * H * W < (1LL << 31),
+// any_size: the *_any entry points take every H, W >= 1; the strict ones keep whole MCUs as their contract
+static int check_shape(const char* what, int B, int H, int W, bool any_size = false) {
+    if (any_size)
+        HY_REQUIRE(B >= 1 && H >= 1 && W >= 1 && H <= 65535 && W <= 65535, HYRES_E_SHAPE,
+                   "%s: B >= 1, 1 <= H, W < 65536 (got %d x %d x %d)", what, B, H, W);
+    else
+        HY_REQUIRE(B >= 1 && H >= 8 && W >= 16 && H % 8 == 0 && W % 16 == 0 && H <= 65528 && W <= 65520, HYRES_E_SHAPE,
+                   "%s: B >= 1, H %% 8 == 0, W %% 16 == 0, H, W < 65536 (got %d x %d x %d)", what, B, H, W);
+    HY_REQUIRE((long long)blocks_per_image(H, W) * kMaxBlockBits < (1LL << 31) &&
+                   (long long)B * padded_h(H) * padded_w(W) < (1LL << 31),
                HYRES_E_SHAPE, "%s: %d x %d x %d is too large", what, B, H, W);
     return ok();
 }
@@ -611,36 +628,22 @@ static int check_shape(const char* what, int B, int H, int W) {
 using namespace hyres;
 using namespace hyres::jpeg;
 
-extern "C" {
+// header + the entropy segment at kMaxBlockBits per block with every byte stuffed + EOI
+static long long stream_bytes(int H, int W) { return align256(kHeaderBytes + 2LL * make_layout(1, H, W).nwords * 4 + 2); }
 
-int hyres_jpeg_quant_tables(int quality, unsigned char* lum, unsigned char* chr) {
-    HY_REQUIRE(lum && chr, HYRES_E_ARG, "jpeg_quant_tables: NULL");
-    quant_tables_zigzag(quality, lum, chr);
-    return ok();
-}
-
-long long hyres_jpeg_workspace_bytes(int B, int H, int W) {
-    if (check_shape("jpeg_workspace_bytes", B, H, W)) return -1;
-    return make_layout(B, H, W).end;
-}
-
-long long hyres_jpeg_stream_bytes(int H, int W) {
-    if (check_shape("jpeg_stream_bytes", 1, H, W)) return -1;
-    // header + the entropy segment at kMaxBlockBits per block with every byte stuffed + EOI
-    return align256(kHeaderBytes + 2LL * make_layout(1, H, W).nwords * 4 + 2);
-}
-
-int hyres_jpeg_roundtrip(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
-                         unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
-                         hyres_stream_t s) {
-    HY_REQUIRE(x && decoded && sizes, HYRES_E_ARG, "jpeg_roundtrip: NULL");
-    int rc = check_shape("jpeg_roundtrip", B, H, W);
+// The entry points come in pairs: the strict one checks for whole MCUs and the *_any one does not; both run the
+// one implementation below.
+static int roundtrip(const char* what, bool any_size, const float* x, int B, int H, int W, int quality,
+                     float* decoded, int* sizes, unsigned char* files, long long file_stride, void* ws,
+                     long long ws_bytes, hyres_stream_t s) {
+    HY_REQUIRE(x && decoded && sizes, HYRES_E_ARG, "%s: NULL", what);
+    int rc = check_shape(what, B, H, W, any_size);
     if (rc) return rc;
     const Layout L = make_layout(B, H, W);
-    HY_REQUIRE(ws && ws_bytes >= L.end, HYRES_E_WORKSPACE, "jpeg_roundtrip: workspace %lld < %lld", ws_bytes, L.end);
-    HY_REQUIRE(aligned16(ws) && aligned16(decoded), HYRES_E_ALIGN, "jpeg_roundtrip: alignment");
-    HY_REQUIRE(!files || file_stride >= hyres_jpeg_stream_bytes(H, W), HYRES_E_WORKSPACE,
-               "jpeg_roundtrip: file stride %lld < %lld", file_stride, hyres_jpeg_stream_bytes(H, W));
+    HY_REQUIRE(ws && ws_bytes >= L.end, HYRES_E_WORKSPACE, "%s: workspace %lld < %lld", what, ws_bytes, L.end);
+    HY_REQUIRE(aligned16(ws) && aligned16(decoded), HYRES_E_ALIGN, "%s: alignment", what);
+    HY_REQUIRE(!files || file_stride >= stream_bytes(H, W), HYRES_E_WORKSPACE, "%s: file stride %lld < %lld", what,
+               file_stride, stream_bytes(H, W));
     char* base = (char*)ws;
     int16_t* coef = (int16_t*)(base + L.coef);
     uint8_t *yp = (uint8_t*)(base + L.yp), *cbp = (uint8_t*)(base + L.cbp), *crp = (uint8_t*)(base + L.crp);
@@ -661,8 +664,8 @@ int hyres_jpeg_roundtrip(const float* x, int B, int H, int W, int quality, float
     const int gblk = ceil_div((long long)B * L.nb, kThreads);
     hipLaunchKernelGGL(jpeg_blocks_kernel, dim3(gblk), dim3(kThreads), 0, st, x, B, H, W, Q, coef, yp, cbp, crp);
     if ((rc = HY_LAUNCH_CHECK("jpeg_blocks"))) return rc;
-    hipLaunchKernelGGL(jpeg_decode_kernel, dim3(ceil_div((long long)B * H * (W / 2), kThreads)), dim3(kThreads), 0, st,
-                       yp, cbp, crp, B, H, W, decoded);
+    hipLaunchKernelGGL(jpeg_decode_kernel, dim3(ceil_div((long long)B * H * ((W + 1) / 2), kThreads)), dim3(kThreads),
+                       0, st, yp, cbp, crp, B, H, W, padded_h(H), padded_w(W), decoded);
     if ((rc = HY_LAUNCH_CHECK("jpeg_decode"))) return rc;
     hipLaunchKernelGGL(jpeg_count_kernel, dim3(gblk), dim3(kThreads), 0, st, coef, B, L.nb, bits);
     if ((rc = HY_LAUNCH_CHECK("jpeg_count"))) return rc;
@@ -684,15 +687,13 @@ int hyres_jpeg_roundtrip(const float* x, int B, int H, int W, int quality, float
     return ok();
 }
 
-int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
-                              unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
-                              hyres_stream_t s) {
-    (void)ws, (void)ws_bytes, (void)s;
-    HY_REQUIRE(x && decoded && sizes, HYRES_E_ARG, "jpeg_roundtrip_host: NULL");
-    int rc = check_shape("jpeg_roundtrip_host", B, H, W);
+static int roundtrip_host(const char* what, bool any_size, const float* x, int B, int H, int W, int quality,
+                          float* decoded, int* sizes, unsigned char* files, long long file_stride) {
+    HY_REQUIRE(x && decoded && sizes, HYRES_E_ARG, "%s: NULL", what);
+    int rc = check_shape(what, B, H, W, any_size);
     if (rc) return rc;
-    HY_REQUIRE(!files || file_stride >= hyres_jpeg_stream_bytes(H, W), HYRES_E_WORKSPACE,
-               "jpeg_roundtrip_host: file stride %lld < %lld", file_stride, hyres_jpeg_stream_bytes(H, W));
+    HY_REQUIRE(!files || file_stride >= stream_bytes(H, W), HYRES_E_WORKSPACE, "%s: file stride %lld < %lld", what,
+               file_stride, stream_bytes(H, W));
     std::vector<uint8_t> f;
     const long long img = 3LL * H * W;
     for (int b = 0; b < B; ++b) {
@@ -702,15 +703,15 @@ int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, 
     return ok();
 }
 
-int hyres_jpeg_parse(const unsigned char* file, long long nbytes, hyres_jpeg_info* info) {
-    HY_REQUIRE(file && info && nbytes >= 0, HYRES_E_ARG, "jpeg_parse: NULL");
+static int parse(const char* what, bool any_size, const unsigned char* file, long long nbytes, hyres_jpeg_info* info) {
+    HY_REQUIRE(file && info && nbytes >= 0, HYRES_E_ARG, "%s: NULL", what);
     FileInfo fi{};
-    const char* why = parse_file(file, (size_t)nbytes, &fi);
-    if (!why && check_shape("jpeg_parse", 1, fi.H, fi.W)) why = "size outside the codec's limits";
+    const char* why = parse_file(file, (size_t)nbytes, &fi, any_size);
+    if (!why && check_shape(what, 1, fi.H, fi.W, any_size)) why = "size outside the codec's limits";
     if (!why && fi.scan_len >= (1LL << 28)) why = "entropy segment of 256 MiB or more";
     info->supported = why ? 0 : 1;
     if (why) {
-        set_error(HYRES_E_ARG, "jpeg_parse: %s", why);  // the reason, read through hyres_last_error_string
+        set_error(HYRES_E_ARG, "%s: %s", what, why);  // the reason, read through hyres_last_error_string
         return ok();  // an unsupported file is an answer, not a failed call
     }
     info->H = fi.H, info->W = fi.W;
@@ -719,8 +720,8 @@ int hyres_jpeg_parse(const unsigned char* file, long long nbytes, hyres_jpeg_inf
     return ok();
 }
 
-static int check_decode(const char* what, int B, int H, int W, long long capacity, int& sub_bits) {
-    int rc = check_shape(what, B, H, W);
+static int check_decode(const char* what, bool any_size, int B, int H, int W, long long capacity, int& sub_bits) {
+    int rc = check_shape(what, B, H, W, any_size);
     if (rc) return rc;
     HY_REQUIRE(capacity >= 1 && capacity < (1LL << 28), HYRES_E_SHAPE, "%s: scan capacity %lld outside 1 .. 2^28 - 1",
                what, capacity);
@@ -730,25 +731,25 @@ static int check_decode(const char* what, int B, int H, int W, long long capacit
     return ok();
 }
 
-long long hyres_jpeg_decode_workspace_bytes(int B, int H, int W, long long scan_capacity) {
+static long long decode_workspace_bytes(const char* what, bool any_size, int B, int H, int W, long long scan_capacity) {
     int sub = 0;
-    if (check_decode("jpeg_decode_workspace_bytes", B, H, W, scan_capacity, sub)) return -1;
+    if (check_decode(what, any_size, B, H, W, scan_capacity, sub)) return -1;
     return make_dec_layout(B, H, W, scan_capacity).end;
 }
 
-int hyres_jpeg_decode(const unsigned char* scans, const long long* scan_off, const int* scan_len,
-                      const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
-                      int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
-                      hyres_stream_t s) {
-    HY_REQUIRE(scans && scan_off && scan_len && qtabs && decoded && status, HYRES_E_ARG, "jpeg_decode: NULL");
-    int rc = check_decode("jpeg_decode", B, H, W, scan_capacity, sub_bits);
+static int decode(const char* what, bool any_size, const unsigned char* scans, const long long* scan_off,
+                  const int* scan_len, const unsigned char* qtabs, int B, int H, int W, long long scan_capacity,
+                  int sub_bits, int block_threads, float* decoded, int* status, int* rounds, void* ws,
+                  long long ws_bytes, hyres_stream_t s) {
+    HY_REQUIRE(scans && scan_off && scan_len && qtabs && decoded && status, HYRES_E_ARG, "%s: NULL", what);
+    int rc = check_decode(what, any_size, B, H, W, scan_capacity, sub_bits);
     if (rc) return rc;
     if (block_threads == 0) block_threads = kSyncThreads;
     HY_REQUIRE(block_threads >= 64 && block_threads <= kMaxSyncThreads && block_threads % 64 == 0, HYRES_E_ARG,
-               "jpeg_decode: block_threads %d: 0 or a multiple of 64 in 64 .. 1024", block_threads);
+               "%s: block_threads %d: 0 or a multiple of 64 in 64 .. 1024", what, block_threads);
     const DecLayout L = make_dec_layout(B, H, W, scan_capacity);
-    HY_REQUIRE(ws && ws_bytes >= L.end, HYRES_E_WORKSPACE, "jpeg_decode: workspace %lld < %lld", ws_bytes, L.end);
-    HY_REQUIRE(aligned16(ws) && aligned16(decoded), HYRES_E_ALIGN, "jpeg_decode: alignment");
+    HY_REQUIRE(ws && ws_bytes >= L.end, HYRES_E_WORKSPACE, "%s: workspace %lld < %lld", what, ws_bytes, L.end);
+    HY_REQUIRE(aligned16(ws) && aligned16(decoded), HYRES_E_ALIGN, "%s: alignment", what);
     char* base = (char*)ws;
     uint8_t* ubytes = (uint8_t*)(base + L.ubytes);
     int *cnt = (int*)(base + L.cnt), *bad = (int*)(base + L.bad), *ulen = (int*)(base + L.ulen);
@@ -778,19 +779,17 @@ int hyres_jpeg_decode(const unsigned char* scans, const long long* scan_off, con
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(ceil_div(L.nb, kThreads), B), dim3(kThreads), 0, st, coef, qtabs, status,
                        H, W, yp, cbp, crp);
     if ((rc = HY_LAUNCH_CHECK("jpeg_idct"))) return rc;
-    hipLaunchKernelGGL(jpeg_decode_kernel, dim3(ceil_div((long long)B * H * (W / 2), kThreads)), dim3(kThreads), 0, st,
-                       yp, cbp, crp, B, H, W, decoded);
+    hipLaunchKernelGGL(jpeg_decode_kernel, dim3(ceil_div((long long)B * H * ((W + 1) / 2), kThreads)), dim3(kThreads),
+                       0, st, yp, cbp, crp, B, H, W, padded_h(H), padded_w(W), decoded);
     if ((rc = HY_LAUNCH_CHECK("jpeg_decode"))) return rc;
     return ok();
 }
 
-int hyres_jpeg_decode_host(const unsigned char* scans, const long long* scan_off, const int* scan_len,
-                           const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
-                           int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
-                           hyres_stream_t s) {
-    (void)block_threads, (void)ws, (void)ws_bytes, (void)s;
-    HY_REQUIRE(scans && scan_off && scan_len && qtabs && decoded && status, HYRES_E_ARG, "jpeg_decode_host: NULL");
-    int rc = check_decode("jpeg_decode_host", B, H, W, scan_capacity, sub_bits);
+static int decode_host(const char* what, bool any_size, const unsigned char* scans, const long long* scan_off,
+                       const int* scan_len, const unsigned char* qtabs, int B, int H, int W, long long scan_capacity,
+                       int sub_bits, float* decoded, int* status, int* rounds) {
+    HY_REQUIRE(scans && scan_off && scan_len && qtabs && decoded && status, HYRES_E_ARG, "%s: NULL", what);
+    int rc = check_decode(what, any_size, B, H, W, scan_capacity, sub_bits);
     if (rc) return rc;
     const long long img = 3LL * H * W;
     for (int b = 0; b < B; ++b) {
@@ -800,6 +799,103 @@ int hyres_jpeg_decode_host(const unsigned char* scans, const long long* scan_off
                                       decoded + b * img, rounds ? rounds + b : nullptr);
     }
     return ok();
+}
+
+extern "C" {
+
+int hyres_jpeg_quant_tables(int quality, unsigned char* lum, unsigned char* chr) {
+    HY_REQUIRE(lum && chr, HYRES_E_ARG, "jpeg_quant_tables: NULL");
+    quant_tables_zigzag(quality, lum, chr);
+    return ok();
+}
+
+long long hyres_jpeg_workspace_bytes(int B, int H, int W) {
+    if (check_shape("jpeg_workspace_bytes", B, H, W)) return -1;
+    return make_layout(B, H, W).end;
+}
+long long hyres_jpeg_workspace_bytes_any(int B, int H, int W) {
+    if (check_shape("jpeg_workspace_bytes_any", B, H, W, true)) return -1;
+    return make_layout(B, H, W).end;
+}
+
+long long hyres_jpeg_stream_bytes(int H, int W) {
+    if (check_shape("jpeg_stream_bytes", 1, H, W)) return -1;
+    return stream_bytes(H, W);
+}
+long long hyres_jpeg_stream_bytes_any(int H, int W) {
+    if (check_shape("jpeg_stream_bytes_any", 1, H, W, true)) return -1;
+    return stream_bytes(H, W);
+}
+
+int hyres_jpeg_roundtrip(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                         unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                         hyres_stream_t s) {
+    return roundtrip("jpeg_roundtrip", false, x, B, H, W, quality, decoded, sizes, files, file_stride, ws, ws_bytes, s);
+}
+int hyres_jpeg_roundtrip_any(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                             unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                             hyres_stream_t s) {
+    return roundtrip("jpeg_roundtrip_any", true, x, B, H, W, quality, decoded, sizes, files, file_stride, ws, ws_bytes,
+                     s);
+}
+
+int hyres_jpeg_roundtrip_host(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                              unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                              hyres_stream_t s) {
+    (void)ws, (void)ws_bytes, (void)s;
+    return roundtrip_host("jpeg_roundtrip_host", false, x, B, H, W, quality, decoded, sizes, files, file_stride);
+}
+int hyres_jpeg_roundtrip_any_host(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                                  unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                                  hyres_stream_t s) {
+    (void)ws, (void)ws_bytes, (void)s;
+    return roundtrip_host("jpeg_roundtrip_any_host", true, x, B, H, W, quality, decoded, sizes, files, file_stride);
+}
+
+int hyres_jpeg_parse(const unsigned char* file, long long nbytes, hyres_jpeg_info* info) {
+    return parse("jpeg_parse", false, file, nbytes, info);
+}
+int hyres_jpeg_parse_any(const unsigned char* file, long long nbytes, hyres_jpeg_info* info) {
+    return parse("jpeg_parse_any", true, file, nbytes, info);
+}
+
+long long hyres_jpeg_decode_workspace_bytes(int B, int H, int W, long long scan_capacity) {
+    return decode_workspace_bytes("jpeg_decode_workspace_bytes", false, B, H, W, scan_capacity);
+}
+long long hyres_jpeg_decode_any_workspace_bytes(int B, int H, int W, long long scan_capacity) {
+    return decode_workspace_bytes("jpeg_decode_any_workspace_bytes", true, B, H, W, scan_capacity);
+}
+
+int hyres_jpeg_decode(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                      const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                      int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                      hyres_stream_t s) {
+    return decode("jpeg_decode", false, scans, scan_off, scan_len, qtabs, B, H, W, scan_capacity, sub_bits,
+                  block_threads, decoded, status, rounds, ws, ws_bytes, s);
+}
+int hyres_jpeg_decode_any(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                          const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                          int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                          hyres_stream_t s) {
+    return decode("jpeg_decode_any", true, scans, scan_off, scan_len, qtabs, B, H, W, scan_capacity, sub_bits,
+                  block_threads, decoded, status, rounds, ws, ws_bytes, s);
+}
+
+int hyres_jpeg_decode_host(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                           const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                           int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                           hyres_stream_t s) {
+    (void)block_threads, (void)ws, (void)ws_bytes, (void)s;
+    return decode_host("jpeg_decode_host", false, scans, scan_off, scan_len, qtabs, B, H, W, scan_capacity, sub_bits,
+                       decoded, status, rounds);
+}
+int hyres_jpeg_decode_any_host(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                               const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                               int block_threads, float* decoded, int* status, int* rounds, void* ws,
+                               long long ws_bytes, hyres_stream_t s) {
+    (void)block_threads, (void)ws, (void)ws_bytes, (void)s;
+    return decode_host("jpeg_decode_any_host", true, scans, scan_off, scan_len, qtabs, B, H, W, scan_capacity,
+                       sub_bits, decoded, status, rounds);
 }
 
 }  // extern "C"

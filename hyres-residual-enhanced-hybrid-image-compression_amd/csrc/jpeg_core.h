@@ -8,7 +8,16 @@
 //           division by 8*q -> zigzag -> DC difference / AC run-size Huffman codes, 0xFF stuffing, 1-bit padding;
 //   decode: coefficient * q -> inverse islow DCT with range limiting -> fancy h2v1 upsample ((3a+b+1)>>2,
 //           (3a+c+2)>>2) -> YCbCr -> BGR -> float(v) / 255.
-// Images are whole MCUs (H % 8 == 0, W % 16 == 0): no edge replication, no dummy blocks.
+// Any H x W: an image that is not whole 16x8 MCUs is coded as libjpeg codes it.  Encode: every component's last real
+// row is replicated down to 8 * ceil(H/8) rows and its last real sample to the right (luminance to 8 * ceil(W/8)
+// columns, the full-resolution chroma to 16 * ceil(W/16) columns before the h2v1 average), both by clamping the
+// pixel coordinates; when ceil(W/8) is odd the second luminance block of a row's last MCU lies outside the
+// component and is a dummy block: AC all zero, DC = the quantised DC of the block before it (so its DC difference
+// is 0 and it is the predictor of the next luminance block).  Decode: every block of the scan is entropy-decoded
+// and inverse-transformed into planes of the padded extents; fancy upsampling applies its last-column rule at the
+// last real chroma sample, column ceil(W/2) - 1, and a chroma row of one or two samples (W <= 4) is replicated,
+// not interpolated (jdsample.c picks h2v1_upsample for downsampled_width <= 2); samples outside H x W are never
+// shown.  Whole-MCU images take none of these paths.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -176,27 +185,29 @@ JC_HD void ycc_to_rgb(int y, int cb, int cr, int& r, int& g, int& b) {
 
 // Level-shifted samples of one block.  x is one image, planar [3][H][W] with plane 0 = B, 1 = G, 2 = R.
 // comp 0: luminance block (bx, by) of 8x8 pixels; comp 1 / 2: Cb / Cr block covering 16x8 pixels, downsampled
-// 2:1 horizontally with libjpeg's h2v1 bias (0 on even output columns, 1 on odd ones).
-JC_HD void sample_block(const float* x, int H, int W, int comp, int bx, int by, int* d) {
+// 2:1 horizontally with libjpeg's h2v1 bias (0 on even output columns, 1 on odd ones).  EDGE: the block reaches
+// past the image; pixel coordinates are clamped to the last real row / column (libjpeg's edge replication).
+template <bool EDGE>
+JC_HD void sample_block_at(const float* x, int H, int W, int comp, int bx, int by, int* d) {
     const long long plane = (long long)H * W;
-    if (comp == 0) {
+    const int x0 = bx * (comp ? 16 : 8);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float* p = x + (long long)(by * 8 + r) * W + bx * 8;
+    for (int r = 0; r < 8; ++r) {
+        const int y = by * 8 + r;
+        const float* p = x + (long long)(EDGE && y > H - 1 ? H - 1 : y) * W + (EDGE ? 0 : x0);
+        if (comp == 0) {
 #pragma unroll
-            for (int c = 0; c < 8; ++c)
-                d[r * 8 + c] = rgb_to_y(to_byte(p[2 * plane + c]), to_byte(p[plane + c]), to_byte(p[c])) - 128;
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float* p = x + (long long)(by * 8 + r) * W + bx * 16;
+            for (int c = 0; c < 8; ++c) {
+                const int i = EDGE ? (x0 + c > W - 1 ? W - 1 : x0 + c) : c;
+                d[r * 8 + c] = rgb_to_y(to_byte(p[2 * plane + i]), to_byte(p[plane + i]), to_byte(p[i])) - 128;
+            }
+        } else {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 int v[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const int i = 2 * c + h;
+                    const int i = EDGE ? (x0 + 2 * c + h > W - 1 ? W - 1 : x0 + 2 * c + h) : 2 * c + h;
                     const int R = to_byte(p[2 * plane + i]), G = to_byte(p[plane + i]), B = to_byte(p[i]);
                     v[h] = comp == 1 ? rgb_to_cb(R, G, B) : rgb_to_cr(R, G, B);
                 }
@@ -204,6 +215,13 @@ JC_HD void sample_block(const float* x, int H, int W, int comp, int bx, int by, 
             }
         }
     }
+}
+
+JC_HD void sample_block(const float* x, int H, int W, int comp, int bx, int by, int* d) {
+    if (by * 8 + 8 > H || (bx + 1) * (comp ? 16 : 8) > W)
+        sample_block_at<true>(x, H, W, comp, bx, by, d);
+    else
+        sample_block_at<false>(x, H, W, comp, bx, by, d);
 }
 
 // ---------------------------------------------------------------------------------------------- DCT
@@ -330,9 +348,30 @@ JC_HD void dequant_idct(int* d, const uint16_t* q) {
 }
 
 // ---------------------------------------------------------------------------------------------- block layout
-// Blocks of one image are numbered in scan order: MCU m = my * (W/16) + mx holds blocks 4m .. 4m+3 =
-// Y(2mx, my), Y(2mx+1, my), Cb(mx, my), Cr(mx, my).
-JC_HD int blocks_per_image(int H, int W) { return (H / 8) * (W / 16) * 4; }
+// Blocks of one image are numbered in scan order: MCU m = my * ceil(W/16) + mx holds blocks 4m .. 4m+3 =
+// Y(2mx, my), Y(2mx+1, my), Cb(mx, my), Cr(mx, my); there are ceil(H/8) MCU rows.  The u8 planes between the
+// inverse DCT and the upsampling have the padded extents: Y [padded_h][padded_w], Cb / Cr [padded_h][padded_w / 2].
+JC_HD int mcus_per_row(int W) { return (W + 15) >> 4; }
+JC_HD int block_rows(int H) { return (H + 7) >> 3; }
+JC_HD int padded_w(int W) { return mcus_per_row(W) * 16; }
+JC_HD int padded_h(int H) { return block_rows(H) * 8; }
+JC_HD int blocks_per_image(int H, int W) { return block_rows(H) * mcus_per_row(W) * 4; }
+JC_HD bool whole_mcus(int H, int W) { return H % 8 == 0 && W % 16 == 0; }
+// luminance block bx of a row lies wholly outside the component: a dummy block
+JC_HD bool dummy_block(int comp, int bx, int W) { return comp == 0 && bx * 8 >= W; }
+
+// One block of the encoder: samples -> forward DCT -> quantised natural-order coefficients in d.  A dummy block
+// repeats the quantised DC of the luminance block before it and has no AC.
+JC_HD void encode_block_coefs(const float* x, int H, int W, int comp, int bx, int by, const uint16_t* q, int* d) {
+    const bool dummy = dummy_block(comp, bx, W);
+    sample_block(x, H, W, comp, dummy ? bx - 1 : bx, by, d);
+    fdct_islow(d);
+    quantize(d, q);
+    if (dummy) {
+#pragma unroll
+        for (int i = 1; i < 64; ++i) d[i] = 0;
+    }
+}
 // the previous block of the same component in scan order (its DC is the predictor), or -1 for the first
 JC_HD int dc_predecessor(int blk) {
     const int slot = blk & 3;
@@ -341,9 +380,14 @@ JC_HD int dc_predecessor(int blk) {
     return slot == 0 ? blk - 3 : blk - 4;
 }
 
-// jdsample.c h2v1_fancy_upsample: chroma for output columns 2i and 2i+1 from a row of cw samples
+// jdsample.c h2v1_fancy_upsample: chroma for output columns 2i and 2i+1 from a row of cw real samples; a row of
+// one or two samples is replicated (h2v1_upsample, which jinit_upsampler picks for downsampled_width <= 2)
 JC_HD void upsample_pair(const uint8_t* c, int cw, int i, int& even, int& odd) {
     const int v = c[i];
+    if (cw <= 2) {
+        even = odd = v;
+        return;
+    }
     even = i == 0 ? v : (3 * v + c[i - 1] + 1) >> 2;
     odd = i == cw - 1 ? v : (3 * v + c[i + 1] + 2) >> 2;
 }
@@ -681,20 +725,21 @@ struct ByteSink {
     }
 };
 
-// u8 Y [H][W] and Cb / Cr [H][W/2] planes -> fancy upsample, colour, / 255 into planar [3][H][W] (plane 0 = B)
+// u8 Y [padded_h][padded_w] and Cb / Cr [padded_h][padded_w / 2] planes -> fancy upsample over the ceil(W/2) real
+// chroma samples, colour, / 255 into planar [3][H][W] (plane 0 = B); for odd W the last pair's second sample is dropped
 inline void planes_to_pixels_host(const uint8_t* yp, const uint8_t* cbp, const uint8_t* crp, int H, int W,
                                   float* decoded) {
-    const int cw = W / 2;
+    const int cw = (W + 1) / 2, pw = padded_w(W), pcw = pw / 2;
     const size_t plane = (size_t)H * W;
     for (int r = 0; r < H; ++r)
         for (int i = 0; i < cw; ++i) {
             int cb[2], cr[2];
-            upsample_pair(cbp + (size_t)r * cw, cw, i, cb[0], cb[1]);
-            upsample_pair(crp + (size_t)r * cw, cw, i, cr[0], cr[1]);
-            for (int h = 0; h < 2; ++h) {
+            upsample_pair(cbp + (size_t)r * pcw, cw, i, cb[0], cb[1]);
+            upsample_pair(crp + (size_t)r * pcw, cw, i, cr[0], cr[1]);
+            for (int h = 0; h < 2 && 2 * i + h < W; ++h) {
                 int R, G, B;
                 const size_t o = (size_t)r * W + 2 * i + h;
-                ycc_to_rgb(yp[o], cb[h], cr[h], R, G, B);
+                ycc_to_rgb(yp[(size_t)r * pw + 2 * i + h], cb[h], cr[h], R, G, B);
                 decoded[o] = (float)B / 255.0f;
                 decoded[plane + o] = (float)G / 255.0f;
                 decoded[2 * plane + o] = (float)R / 255.0f;
@@ -708,23 +753,21 @@ inline int roundtrip_image_host(const float* x, int H, int W, int quality, float
                                 std::vector<uint8_t>* file) {
     static const HuffTables T = make_huff_tables();
     const QuantTables Q = quant_tables_natural(quality);
-    const int nb = blocks_per_image(H, W), mw = W / 16, cw = W / 2;
+    const int nb = blocks_per_image(H, W), mw = mcus_per_row(W), ph = padded_h(H), ypw = padded_w(W), cw = ypw / 2;
     std::vector<int16_t> coef((size_t)nb * 64);
-    std::vector<uint8_t> yp((size_t)H * W), cp[2];
-    cp[0].resize((size_t)H * cw);
-    cp[1].resize((size_t)H * cw);
+    std::vector<uint8_t> yp((size_t)ph * ypw), cp[2];
+    cp[0].resize((size_t)ph * cw);
+    cp[1].resize((size_t)ph * cw);
     int d[64];
     for (int blk = 0; blk < nb; ++blk) {
         const int m = blk >> 2, slot = blk & 3, mx = m % mw, my = m / mw;
         const int comp = slot < 2 ? 0 : slot - 1, bx = slot < 2 ? 2 * mx + slot : mx;
         const uint16_t* q = Q.q[comp ? 1 : 0];
-        sample_block(x, H, W, comp, bx, my, d);
-        fdct_islow(d);
-        quantize(d, q);
+        encode_block_coefs(x, H, W, comp, bx, my, q, d);
         for (int k = 0; k < 64; ++k) coef[(size_t)blk * 64 + k] = (int16_t)d[kNatural[k]];
         dequant_idct(d, q);
         uint8_t* plane = comp ? cp[comp - 1].data() : yp.data();
-        const int pw = comp ? cw : W;
+        const int pw = comp ? cw : ypw;
         for (int r = 0; r < 8; ++r)
             for (int c = 0; c < 8; ++c) plane[(size_t)(my * 8 + r) * pw + bx * 8 + c] = (uint8_t)d[r * 8 + c];
     }
@@ -756,9 +799,9 @@ struct FileInfo {
 };
 
 // Parses the marker segments of a JPEG file.  Returns NULL when the decoder takes the file (baseline 8-bit 4:2:2,
-// three components in one interleaved scan, the Annex K Huffman tables, no restart interval, whole MCUs; APPn / COM
-// segments anywhere), else the reason it does not.
-inline const char* parse_file(const uint8_t* f, size_t n, FileInfo* info) {
+// three components in one interleaved scan, the Annex K Huffman tables, no restart interval; APPn / COM segments
+// anywhere; whole MCUs unless any_size), else the reason it does not.
+inline const char* parse_file(const uint8_t* f, size_t n, FileInfo* info, bool any_size = false) {
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return "not a JPEG file (no SOI)";
     uint8_t qt[4][64];
     bool have_qt[4] = {false, false, false, false}, have_ht[2][2] = {{false, false}, {false, false}}, sof = false;
@@ -818,8 +861,8 @@ inline const char* parse_file(const uint8_t* f, size_t n, FileInfo* info) {
                 tq[c] = p[8 + 3 * c];
                 if (tq[c] > 3) return "malformed SOF0";
             }
-            if (info->H <= 0 || info->W <= 0 || info->H % 8 || info->W % 16)
-                return "size is not whole MCUs (H % 8 == 0, W % 16 == 0)";
+            if (info->H <= 0 || info->W <= 0) return "zero height or width";
+            if (!any_size && !whole_mcus(info->H, info->W)) return "size is not whole MCUs (H % 8 == 0, W % 16 == 0)";
             sof = true;
         } else if (m >= 0xC1 && m <= 0xCF && m != 0xC8) {
             return m == 0xC2 ? "progressive file" : "not a baseline (SOF0) file";
@@ -863,7 +906,7 @@ inline int unstuffed_capacity(long long scan_capacity) { return (int)((scan_capa
 inline int decode_image_host(const uint8_t* scan, long long scan_len, long long capacity, const uint8_t qz[2][64],
                              int H, int W, int sub_bits, float* decoded, int* rounds_out) {
     static const DecTables T = make_dec_tables();
-    const int nb = blocks_per_image(H, W), cw = W / 2;
+    const int nb = blocks_per_image(H, W), ph = padded_h(H), ypw = padded_w(W), cw = ypw / 2;
     bool marker_error = false;
     int extra = 0;
     if (scan_len < 0) scan_len = 0;
@@ -918,17 +961,17 @@ inline int decode_image_host(const uint8_t* scan, long long scan_len, long long 
     uint16_t q[2][64];
     for (int c = 0; c < 2; ++c)
         for (int k = 0; k < 64; ++k) q[c][kNatural[k]] = qz[c][k];
-    std::vector<uint8_t> yp((size_t)H * W), cp[2];
-    cp[0].resize((size_t)H * cw);
-    cp[1].resize((size_t)H * cw);
-    const int mw = W / 16;
+    std::vector<uint8_t> yp((size_t)ph * ypw), cp[2];
+    cp[0].resize((size_t)ph * cw);
+    cp[1].resize((size_t)ph * cw);
+    const int mw = mcus_per_row(W);
     int d[64];
     for (int blk = 0; blk < nb; ++blk) {
         const int m = blk >> 2, slot = blk & 3, mx = m % mw, my = m / mw;
         const int comp = slot < 2 ? 0 : slot - 1, bx = slot < 2 ? 2 * mx + slot : mx;
         coef_block_to_samples(coef.data() + (size_t)blk * 64, q[comp ? 1 : 0], d);
         uint8_t* plane = comp ? cp[comp - 1].data() : yp.data();
-        const int pw = comp ? cw : W;
+        const int pw = comp ? cw : ypw;
         for (int r = 0; r < 8; ++r)
             for (int c = 0; c < 8; ++c) plane[(size_t)(my * 8 + r) * pw + bx * 8 + c] = (uint8_t)d[r * 8 + c];
     }

@@ -199,6 +199,23 @@ __global__ void add2d_kernel(const float* x, int ldx, float* y, int ldy, long lo
         stv<YH>(y, p * ldy + c, v);
     }
 }
+// NHWC [B][Hs][Ws][C] (pixel stride ldx) -> [B][Hd][Wd][C] (ldy), both anchored at the top-left corner: destination
+// pixels outside the source read as zero (a zero pad at the bottom and right), source pixels outside the
+// destination are dropped (a crop); each is the other's gradient
+template <bool XH = false, bool YH = false>
+__global__ void pad2d_kernel(const float* x, int ldx, int Hs, int Ws, float* y, int ldy, int Hd, int Wd, int B, int C,
+                             int acc) {
+    const long long n = (long long)B * Hd * Wd * C;
+    GRID_STRIDE(i, n) {
+        const long long p = i / C;  // (b * Hd + h) * Wd + w
+        const int c = (int)(i - p * C);
+        const long long row = p / Wd;
+        const int w = (int)(p - row * Wd), b = (int)(row / Hd), h = (int)(row - (long long)b * Hd);
+        float v = h < Hs && w < Ws ? ldv<XH>(x, (((long long)b * Hs + h) * Ws + w) * ldx + c) : 0.f;
+        if (acc) v += ldv<YH>(y, p * ldy + c);
+        stv<YH>(y, p * ldy + c, v);
+    }
+}
 // float4 variants of the [P][C]-strided elementwise passes (C, every ld % 4 == 0, 16B-aligned, P*C < 2^31):
 // 32-bit index math, 16 B per lane (8 B for fp16 operands)
 template <bool XH = false, bool YH = false>
@@ -700,6 +717,29 @@ int hyres_add2d(const void* x, int ldx, void* y, int ldy, long long P, int C, in
         case HYRES_IO_Y16: return add2d_impl<false, true>(xf, ldx, yf, ldy, P, C, accumulate, s);
         case HYRES_IO_X16 | HYRES_IO_Y16: return add2d_impl<true, true>(xf, ldx, yf, ldy, P, C, accumulate, s);
         default: return add2d_impl<false, false>(xf, ldx, yf, ldy, P, C, accumulate, s);
+    }
+}
+extern "C++" {
+template <bool XH, bool YH>
+static int pad2d_impl(const void* x, int ldx, int Hs, int Ws, void* y, int ldy, int Hd, int Wd, int B, int C,
+                      int accumulate, hyres_stream_t s) {
+    hipLaunchKernelGGL((pad2d_kernel<XH, YH>), dim3(grid_for((long long)B * Hd * Wd * C)), dim3(256), 0, as_stream(s),
+                       (const float*)x, ldx, Hs, Ws, (float*)y, ldy, Hd, Wd, B, C, accumulate);
+    return HY_LAUNCH_CHECK("pad2d");
+}
+}  // extern "C++"
+int hyres_pad2d(const void* x, int ldx, int Hs, int Ws, void* y, int ldy, int Hd, int Wd, int B, int C,
+                int accumulate, int io, hyres_stream_t s) {
+    HY_REQUIRE(io >= 0 && io <= (HYRES_IO_X16 | HYRES_IO_Y16), HYRES_E_ARG, "pad2d: io %d", io);
+    HY_REQUIRE(x && y, HYRES_E_ARG, "pad2d: NULL");
+    HY_REQUIRE(B >= 1 && C >= 1 && Hs >= 1 && Ws >= 1 && Hd >= 1 && Wd >= 1 && ldx >= C && ldy >= C, HYRES_E_SHAPE,
+               "pad2d: B %d, C %d, %d x %d (ld %d) -> %d x %d (ld %d)", B, C, Hs, Ws, ldx, Hd, Wd, ldy);
+    switch (io) {
+        case HYRES_IO_X16: return pad2d_impl<true, false>(x, ldx, Hs, Ws, y, ldy, Hd, Wd, B, C, accumulate, s);
+        case HYRES_IO_Y16: return pad2d_impl<false, true>(x, ldx, Hs, Ws, y, ldy, Hd, Wd, B, C, accumulate, s);
+        case HYRES_IO_X16 | HYRES_IO_Y16:
+            return pad2d_impl<true, true>(x, ldx, Hs, Ws, y, ldy, Hd, Wd, B, C, accumulate, s);
+        default: return pad2d_impl<false, false>(x, ldx, Hs, Ws, y, ldy, Hd, Wd, B, C, accumulate, s);
     }
 }
 int hyres_mul(const float* a, const float* b, float* y, long long n, hyres_stream_t s) {

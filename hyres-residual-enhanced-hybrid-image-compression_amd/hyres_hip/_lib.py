@@ -129,6 +129,7 @@ _SIGS = {
     "hyres_accumulate": (_I, [_P, _P, _LL, _I, _P]),
     "hyres_scale": (_I, [_P, _P, _F, _P, _LL, _I, _P]),
     "hyres_add2d": (_I, [_P, _I, _P, _I, _LL, _I, _I, _I, _P]),
+    "hyres_pad2d": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "hyres_mul": (_I, [_P, _P, _P, _LL, _P]),
     "hyres_zero": (_I, [_P, _LL, _P]),
     "hyres_gdn_reparam_fwd": (_I, [_P, _P, _P, _P, _I, _P]),
@@ -168,6 +169,14 @@ _SIGS = {
     "hyres_jpeg_decode_workspace_bytes": (_LL, [_I, _I, _I, _LL]),
     "hyres_jpeg_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _LL, _P]),
     "hyres_jpeg_decode_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _LL, _P]),
+    "hyres_jpeg_workspace_bytes_any": (_LL, [_I, _I, _I]),
+    "hyres_jpeg_stream_bytes_any": (_LL, [_I, _I]),
+    "hyres_jpeg_roundtrip_any": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P]),
+    "hyres_jpeg_roundtrip_any_host": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P]),
+    "hyres_jpeg_parse_any": (_I, [_P, _LL, ctypes.POINTER(JpegInfo)]),
+    "hyres_jpeg_decode_any_workspace_bytes": (_LL, [_I, _I, _I, _LL]),
+    "hyres_jpeg_decode_any": (_I, [_P, _P, _P, _P, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _LL, _P]),
+    "hyres_jpeg_decode_any_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _LL, _P]),
     "hyres_msssim_workspace_bytes": (_LL, [_I, _I, _I, _I, _I]),
     "hyres_msssim": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),
     "hyres_msssim_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _LL, _P]),

@@ -16,6 +16,10 @@ models/utils/turbo_jpeg_compression.py as HIP kernels (csrc/jpeg.hip), bit-exact
 ``roundtrip_host`` / ``encode_host`` / ``decode_host`` run the same arithmetic (csrc/jpeg_core.h) on CPU tensors through
 the pure-host C-ABI; they exist to pin the codec against Pillow's libjpeg-turbo where no GPU is present.
 ``decode_host`` runs the decoder's very schedule (rounds over subsequences), a loop where the kernel has threads.
+
+``any_size=True`` on any of these takes every H x W >= 1 x 1 through the ``*_any`` entry points (partial MCUs coded as
+libjpeg codes them: edge replication, dummy blocks, the true size in SOF0); the default keeps whole MCUs
+(H % 8 == 0, W % 16 == 0) as the contract, and everything else stays with the caller's host path.
 """
 from __future__ import annotations
 
@@ -28,16 +32,36 @@ import torch
 from . import _lib as L
 
 
-def supported_shape(x: torch.Tensor) -> bool:
-    """3-channel fp32 NCHW with whole 16x8 MCUs (no edge replication, no dummy blocks)."""
-    return (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 4
-            and x.size(0) >= 1 and x.size(1) == 3 and x.size(2) >= 8 and x.size(3) >= 16
-            and x.size(2) % 8 == 0 and x.size(3) % 16 == 0)
+def supported_shape(x: torch.Tensor, any_size: bool = False) -> bool:
+    """3-channel fp32 NCHW with whole 16x8 MCUs; any_size: any H, W in 1 .. 65535."""
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 4
+            and x.size(0) >= 1 and x.size(1) == 3):
+        return False
+    if any_size:
+        return 1 <= x.size(2) <= 65535 and 1 <= x.size(3) <= 65535
+    return x.size(2) >= 8 and x.size(3) >= 16 and x.size(2) % 8 == 0 and x.size(3) % 16 == 0
 
 
-def supported(x: torch.Tensor) -> bool:
+def supported(x: torch.Tensor, any_size: bool = False) -> bool:
     """The device path takes ``x``: a supported shape, on the GPU."""
-    return supported_shape(x) and x.is_cuda
+    return supported_shape(x, any_size) and x.is_cuda
+
+
+_ANY = {
+    "hyres_jpeg_workspace_bytes": "hyres_jpeg_workspace_bytes_any",
+    "hyres_jpeg_stream_bytes": "hyres_jpeg_stream_bytes_any",
+    "hyres_jpeg_roundtrip": "hyres_jpeg_roundtrip_any",
+    "hyres_jpeg_roundtrip_host": "hyres_jpeg_roundtrip_any_host",
+    "hyres_jpeg_parse": "hyres_jpeg_parse_any",
+    "hyres_jpeg_decode_workspace_bytes": "hyres_jpeg_decode_any_workspace_bytes",
+    "hyres_jpeg_decode": "hyres_jpeg_decode_any",
+    "hyres_jpeg_decode_host": "hyres_jpeg_decode_any_host",
+}
+
+
+def _any(name: str, any_size: bool) -> str:
+    """The C-ABI name of an entry point or of its any-size twin."""
+    return _ANY[name] if any_size else name
 
 
 def quant_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -47,36 +71,37 @@ def quant_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
     return lum, chr_
 
 
-def stream_bytes(H: int, W: int) -> int:
-    n = L.load().hyres_jpeg_stream_bytes(int(H), int(W))
+def stream_bytes(H: int, W: int, any_size: bool = False) -> int:
+    name = _any("hyres_jpeg_stream_bytes", any_size)
+    n = getattr(L.load(), name)(int(H), int(W))
     if n < 0:
-        L.check(1, "hyres_jpeg_stream_bytes")
+        L.check(1, name)
     return int(n)
 
 
-def _run(x: torch.Tensor, quality: int, files: bool):
-    if not supported(x):
+def _run(x: torch.Tensor, quality: int, files: bool, any_size: bool = False):
+    if not supported(x, any_size):
         raise ValueError(f"jpeg_device: unsupported input {tuple(x.shape)} {x.dtype} on {x.device} "
-                         "(3-channel fp32 NCHW on the GPU, H % 8 == 0, W % 16 == 0)")
+                         "(3-channel fp32 NCHW on the GPU" + ("" if any_size else ", H % 8 == 0, W % 16 == 0") + ")")
     from .ops import Workspace
     x = x.detach().contiguous()
     N, _, H, W = x.shape
-    lib = L.load()
-    nws = lib.hyres_jpeg_workspace_bytes(N, H, W)
+    name = _any("hyres_jpeg_workspace_bytes", any_size)
+    nws = getattr(L.load(), name)(N, H, W)
     if nws < 0:
-        L.check(1, "hyres_jpeg_workspace_bytes")
+        L.check(1, name)
     ws = Workspace.get(int(nws), x.device, "jpeg")
     decoded = torch.empty_like(x)
     sizes = torch.empty(N, dtype=torch.int32, device=x.device)
-    stride = stream_bytes(H, W) if files else 0
+    stride = stream_bytes(H, W, any_size) if files else 0
     buf = torch.empty((N, stride), dtype=torch.uint8, device=x.device) if files else None
-    L.call("hyres_jpeg_roundtrip", x.data_ptr(), N, H, W, int(quality), decoded.data_ptr(), sizes.data_ptr(),
+    L.call(_any("hyres_jpeg_roundtrip", any_size), x.data_ptr(), N, H, W, int(quality), decoded.data_ptr(), sizes.data_ptr(),
            L.ptr(buf), stride, ws.data_ptr(), ws.numel(), L.stream())
     return decoded, sizes, buf
 
 
-def roundtrip(x: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    decoded, sizes, _ = _run(x, quality, False)
+def roundtrip(x: torch.Tensor, quality: int, any_size: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    decoded, sizes, _ = _run(x, quality, False, any_size)
     return decoded, sizes
 
 
@@ -90,64 +115,66 @@ def _split(buf: torch.Tensor, sizes) -> List[bytes]:
     return [buf[i, :int(n)].numpy().tobytes() for i, n in enumerate(sizes)]
 
 
-def encode(x: torch.Tensor, quality: int) -> Tuple[torch.Tensor, List[bytes]]:
-    decoded, sizes, buf = _run(x, quality, True)
+def encode(x: torch.Tensor, quality: int, any_size: bool = False) -> Tuple[torch.Tensor, List[bytes]]:
+    decoded, sizes, buf = _run(x, quality, True, any_size)
     sizes_h = sizes.cpu().tolist()
     # one device-to-host copy of the used prefix of every file
     return decoded, _split(buf[:, :max(sizes_h)].cpu(), sizes_h)
 
 
 # ---------------------------------------------------------------------------------------------- host (CPU tensors)
-def _run_host(x: torch.Tensor, quality: int, files: bool):
+def _run_host(x: torch.Tensor, quality: int, files: bool, any_size: bool = False):
     if x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.size(1) != 3:
         raise ValueError("jpeg_device.roundtrip_host: 3-channel fp32 NCHW CPU tensor")
     x = x.detach().contiguous()
     N, _, H, W = x.shape
     decoded = torch.empty_like(x)
     sizes = torch.empty(N, dtype=torch.int32)
-    stride = stream_bytes(H, W) if files else 0
+    stride = stream_bytes(H, W, any_size) if files else 0
     buf = torch.empty((N, stride), dtype=torch.uint8) if files else None
-    L.call("hyres_jpeg_roundtrip_host", x.data_ptr(), N, H, W, int(quality), decoded.data_ptr(), sizes.data_ptr(),
+    L.call(_any("hyres_jpeg_roundtrip_host", any_size), x.data_ptr(), N, H, W, int(quality), decoded.data_ptr(), sizes.data_ptr(),
            L.ptr(buf), stride, None, 0, ctypes.c_void_p(None))
     return decoded, sizes, buf
 
 
-def roundtrip_host(x: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    decoded, sizes, _ = _run_host(x, quality, False)
+def roundtrip_host(x: torch.Tensor, quality: int, any_size: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    decoded, sizes, _ = _run_host(x, quality, False, any_size)
     return decoded, sizes
 
 
-def encode_host(x: torch.Tensor, quality: int) -> Tuple[torch.Tensor, List[bytes]]:
-    decoded, sizes, buf = _run_host(x, quality, True)
+def encode_host(x: torch.Tensor, quality: int, any_size: bool = False) -> Tuple[torch.Tensor, List[bytes]]:
+    decoded, sizes, buf = _run_host(x, quality, True, any_size)
     return decoded, _split(buf, sizes.tolist())
 
 
 # ---------------------------------------------------------------------------------------------- decoding files
-def _parse(data) -> Tuple[Optional[L.JpegInfo], Optional[str]]:
+def _parse(data, any_size: bool = False) -> Tuple[Optional[L.JpegInfo], Optional[str]]:
     data = bytes(data)
     info = L.JpegInfo()
-    L.call("hyres_jpeg_parse", data, len(data), ctypes.byref(info))
+    L.call(_any("hyres_jpeg_parse", any_size), data, len(data), ctypes.byref(info))
     if info.supported:
         return info, None
     return None, L.load().hyres_last_error_string().decode()
 
 
-def unsupported_reason(data) -> Optional[str]:
+def unsupported_reason(data, any_size: bool = False) -> Optional[str]:
     """None when the device decoder takes the file, else why it does not (the file keeps the host decoder)."""
-    return _parse(data)[1]
+    return _parse(data, any_size)[1]
 
 
-def supported_file(data) -> bool:
-    """Baseline 8-bit 4:2:2 with the Annex K Huffman tables, one interleaved scan, no restart interval, whole MCUs."""
-    return _parse(data)[0] is not None
+def supported_file(data, any_size: bool = False) -> bool:
+    """Baseline 8-bit 4:2:2 with the Annex K Huffman tables, one interleaved scan, no restart interval; whole MCUs
+    unless ``any_size``."""
+    return _parse(data, any_size)[0] is not None
 
 
 class Staged:
     """N files of one size ready for ``decode_tensors``: one uint8 buffer holding the scan offsets (int64), lengths
     (int32), quantisers [N,2,64] and the raw entropy segments; ``capacity`` bounds every segment's length."""
 
-    def __init__(self, buf: torch.Tensor, N: int, H: int, W: int, capacity: int, room: int):
+    def __init__(self, buf: torch.Tensor, N: int, H: int, W: int, capacity: int, room: int, any_size: bool = False):
         self.buf, self.N, self.H, self.W, self.capacity, self.room = buf, N, H, W, capacity, room
+        self.any_size = any_size
         self.o_len, self.o_q, self.o_scans = self.layout(N)[:3]
 
     @staticmethod
@@ -180,7 +207,8 @@ def _pinned_for(nbytes: int, device: torch.device) -> torch.Tensor:
     return ent[0]
 
 
-def stage(files: Sequence, device=None, capacity: Optional[int] = None, room: Optional[int] = None) -> Staged:
+def stage(files: Sequence, device=None, capacity: Optional[int] = None, room: Optional[int] = None,
+          any_size: bool = False) -> Staged:
     """Parse ``files`` (bytes each) and lay their entropy segments out for the decoder; on a GPU ``device`` with one
     pinned upload, else (None / CPU) as a host buffer.  ``capacity`` / ``room`` fix the longest segment / the bytes of
     all segments the buffer can take (for a static buffer refilled between graph replays)."""
@@ -189,7 +217,7 @@ def stage(files: Sequence, device=None, capacity: Optional[int] = None, room: Op
         raise ValueError("jpeg_device.stage: no files")
     infos = []
     for i, d in enumerate(datas):
-        info, why = _parse(d)
+        info, why = _parse(d, any_size)
         if info is None:
             raise ValueError(f"jpeg_device: file {i} is not supported by the device decoder: {why}")
         infos.append(info)
@@ -217,12 +245,12 @@ def stage(files: Sequence, device=None, capacity: Optional[int] = None, room: Op
     h[o_len:o_len + 4 * N].view(np.int32)[:] = lens
     h[o_q:o_q + 128 * N] = np.concatenate([np.frombuffer(bytes(f.qtab), np.uint8) for f in infos])
     if not on_gpu:
-        return Staged(host, N, H, W, capacity, room)
+        return Staged(host, N, H, W, capacity, room, any_size)
     device = torch.device(device)
     buf = torch.empty(total, dtype=torch.uint8, device=device)
     buf.copy_(host, non_blocking=True)  # the one upload
     _pinned[(device.index, torch.cuda.current_stream(device).cuda_stream)][1].record()
-    return Staged(buf, N, H, W, capacity, room)
+    return Staged(buf, N, H, W, capacity, room, any_size)
 
 
 def decode_tensors(st: Staged, sub_bits: int = 0, block_threads: int = 0):
@@ -232,14 +260,15 @@ def decode_tensors(st: Staged, sub_bits: int = 0, block_threads: int = 0):
     dev = st.buf.device
     if dev.type != "cuda":
         raise ValueError("jpeg_device.decode_tensors: the staged batch is not on the GPU (decode_host decodes there)")
-    nws = L.load().hyres_jpeg_decode_workspace_bytes(st.N, st.H, st.W, st.capacity)
+    name = _any("hyres_jpeg_decode_workspace_bytes", st.any_size)
+    nws = getattr(L.load(), name)(st.N, st.H, st.W, st.capacity)
     if nws < 0:
-        L.check(1, "hyres_jpeg_decode_workspace_bytes")
+        L.check(1, name)
     ws = Workspace.get(int(nws), dev, "jpeg_decode")
     decoded = torch.empty((st.N, 3, st.H, st.W), dtype=torch.float32, device=dev)
     status = torch.empty(st.N, dtype=torch.int32, device=dev)
     rounds = torch.empty(st.N, dtype=torch.int32, device=dev)
-    L.call("hyres_jpeg_decode", st.scans.data_ptr(), st.scan_off.data_ptr(), st.scan_len.data_ptr(),
+    L.call(_any("hyres_jpeg_decode", st.any_size), st.scans.data_ptr(), st.scan_off.data_ptr(), st.scan_len.data_ptr(),
            st.qtabs.data_ptr(), st.N, st.H, st.W, st.capacity, int(sub_bits), int(block_threads), decoded.data_ptr(),
            status.data_ptr(), rounds.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
     return decoded, status, rounds
@@ -252,23 +281,24 @@ def _raise_on_status(status: List[int]) -> None:
                          + ", ".join(f"{i} (status {s})" for i, s in bad))
 
 
-def decode(files: Sequence, device, sub_bits: int = 0, check: bool = True):
+def decode(files: Sequence, device, sub_bits: int = 0, check: bool = True, any_size: bool = False):
     """JPEG files (bytes) of one size -> [N,3,H,W] fp32 on ``device``.  check: read the N status words back and
     raise ValueError naming the corrupt images; check=False returns (decoded, status), both on the device."""
-    decoded, status, _ = decode_tensors(stage(files, device), sub_bits)
+    decoded, status, _ = decode_tensors(stage(files, device, any_size=any_size), sub_bits)
     if not check:
         return decoded, status
     _raise_on_status(status.cpu().tolist())
     return decoded
 
 
-def decode_host(files: Sequence, sub_bits: int = 0, check: bool = True, return_rounds: bool = False):
+def decode_host(files: Sequence, sub_bits: int = 0, check: bool = True, return_rounds: bool = False,
+                any_size: bool = False):
     """``decode`` on the host twin (CPU tensors): the same rounds, write pass, DC scan and IDCT, no GPU call."""
-    st = stage(files, None)
+    st = stage(files, None, any_size=any_size)
     decoded = torch.empty((st.N, 3, st.H, st.W), dtype=torch.float32)
     status = torch.empty(st.N, dtype=torch.int32)
     rounds = torch.empty(st.N, dtype=torch.int32)
-    L.call("hyres_jpeg_decode_host", st.scans.data_ptr(), st.scan_off.data_ptr(), st.scan_len.data_ptr(),
+    L.call(_any("hyres_jpeg_decode_host", any_size), st.scans.data_ptr(), st.scan_off.data_ptr(), st.scan_len.data_ptr(),
            st.qtabs.data_ptr(), st.N, st.H, st.W, st.capacity, int(sub_bits), 0, decoded.data_ptr(),
            status.data_ptr(), rounds.data_ptr(), None, 0, ctypes.c_void_p(None))
     if check:

@@ -309,6 +309,28 @@ def add(tape: Optional[Tape], a: Node, b: Node, alpha: float = 1.0) -> Node:
     return y
 
 
+def pad2d(tape: Optional[Tape], x: Node, Hd: int, Wd: int) -> Node:
+    """x [B,H,W,C] -> [B,Hd,Wd,C] anchored at the top-left corner: a zero pad at the bottom and right where the
+    target is larger, a crop where it is smaller.  ResidualJPEGCompression pads the residual of an image whose sides
+    are not multiples of the transforms' stride and crops residual_hat back; the backward of either is the other."""
+    y = Node.new(x.B, Hd, Wd, x.C, x.device, rg=x.rg, dtype=x.v.dtype)
+    L.call("hyres_pad2d", x.ptr(), x.ld, x.H, x.W, y.ptr(), y.ld, Hd, Wd, x.B, x.C, 0,
+           L.dt_mask(x, y, L.IO_X16, L.IO_Y16), L.stream())
+    if tape is None:
+        return y
+
+    def bwd():
+        g = y.grad()
+        if g is None or not x.rg:
+            return
+        tgt, acc = x.grad_target()
+        L.call("hyres_pad2d", g.data_ptr(), y.grad_ld(), Hd, Wd, tgt.data_ptr(), x.grad_ld(), x.H, x.W, x.B, x.C, acc,
+               L.dt_mask(g, tgt, L.IO_X16, L.IO_Y16), L.stream())
+
+    tape.push(bwd)
+    return y
+
+
 def add_clamp01(tape: Optional[Tape], x0: Node, r: Node) -> Node:
     """x_hat = clamp(x0 + r, 0, 1)  (models/hyres.py:66-67)."""
     n = x0.P * x0.C

@@ -74,6 +74,16 @@ class LightWeightCheckerboard(CompressionModel):
         self.param_aggregation = Sequential(
             conv1x1(4 * M, 640), ReLU(inplace=True), conv1x1(640, 512), ReLU(inplace=True), conv1x1(512, 2 * M))
 
+    @property
+    def stride(self) -> int:
+        """Input rows / columns per hyper-latent sample: the product of the strides of g_a and h_a (8 * 4 = 32).  The
+        sides of the input are multiples of it."""
+        s = 1
+        for m in list(self.g_a) + list(self.h_a):
+            if isinstance(m, torch.nn.Conv2d):
+                s *= m.stride[0]
+        return s
+
     # ------------------------------------------------------------------ HIP graph
     def _g_a(self, tape, x: Node) -> Node:
         """g_a; under autocast inference its layers above the latent resolution keep fp16 activations in

@@ -6,6 +6,13 @@ a host stage (libjpeg-turbo) by default, or the bit-exact device codec (hyres_hi
 ``TurboJPEGCompression.device_codec`` is on; everything after the host->device copy — residual, LightWeightCheckerboard,
 x_hat_initial, MultiScaleRefine, clamp — is ONE HIP tape (forward and backward on MI355X).
 
+Images of any size: the base layer is a real JPEG of the real H x W image; only the learned residual is padded.  With
+S = ``residual_model.stride`` (32), ``residual`` is zero-padded at the bottom and right to multiples of S
+(refine_ops.pad2d, one op on the tape), coded by the residual model unchanged, and ``residual_hat`` is cropped back
+before ``x_hat_initial``; MultiScaleRefine runs at the true size.  ``likelihoods`` keep the padded latent's shape and
+callers divide by the true pixel count; ``decompress`` reads H x W from the decoded JPEG.  An aligned input records no
+pad op and launches no kernel for it.
+
 Fixed reference bugs (documented in DESIGN.md):
   * load_state_dict kept the ``refine.`` prefix and strict-loaded into ``self.refine`` (:150-163), so the
     model could not reload its own state_dict; here prefixes are stripped per sub-module;
@@ -36,10 +43,21 @@ class ResidualJPEGCompression(CompressionModel):
         self.residual_model = base_model if base_model is not None else LightWeightCheckerboard(**kwargs)
         self.refine = MultiScaleRefine(in_channels=3, mid_channels=64)
 
+    def padded_size(self, H: int, W: int) -> Tuple[int, int]:
+        """H, W rounded up to multiples of the residual model's stride: the size the residual is coded at."""
+        S = int(getattr(self.residual_model, "stride", 32))
+        return -(-H // S) * S, -(-W // S) * S
+
     # ------------------------------------------------------------------ HIP graph (device part)
     def hip(self, tape, x: O.Node, jpeg: O.Node, training: bool, noisequant: bool):
         residual = R.add(tape, x, jpeg, alpha=-1.0)                       # hyres.py:48
-        residual_hat, y_lik, z_lik = self.residual_model.hip(tape, residual, training, noisequant)
+        Hp, Wp = self.padded_size(x.H, x.W)
+        if (Hp, Wp) == (x.H, x.W):
+            residual_hat, y_lik, z_lik = self.residual_model.hip(tape, residual, training, noisequant)
+        else:  # pad the residual, not the image: zeros are the cheapest thing for the entropy model to code
+            padded_hat, y_lik, z_lik = self.residual_model.hip(tape, R.pad2d(tape, residual, Hp, Wp), training,
+                                                               noisequant)
+            residual_hat = R.pad2d(tape, padded_hat, x.H, x.W)
         x0 = R.add(tape, jpeg, residual_hat)                              # hyres.py:62
         O.GradReady.mark(tape, "refine")  # backward: refine's gradients complete past this point
         with O.f16_region():  # fp16 activations under autocast inference (configs[4])
@@ -98,13 +116,17 @@ class ResidualJPEGCompression(CompressionModel):
         device = next(self.parameters()).device
         if self.jpeg.on_device(x) and x.device == device:
             # device codec: the decoded base layer of the round trip is what the decoder will reconstruct
-            jpeg_decoded, datas = jpeg_device.encode(x.detach(), self.jpeg.quality)
+            jpeg_decoded, datas = jpeg_device.encode(x.detach(), self.jpeg.quality, self.jpeg.any_size)
             jpeg_buffers = [io.BytesIO(d) for d in datas]
         else:
             x_cpu = x.detach().cpu() if x.device.type != "cpu" else x
             jpeg_buffers = self.jpeg.compress(x_cpu)
             jpeg_decoded = self.jpeg.decompress(jpeg_buffers, device)
         residual = x.to(device) - jpeg_decoded
+        H, W = residual.shape[-2:]
+        Hp, Wp = self.padded_size(H, W)
+        if (Hp, Wp) != (H, W):
+            residual = torch.nn.functional.pad(residual, (0, Wp - W, 0, Hp - H))
         residual_compressed = self.residual_model.compress(residual)
         residual_compressed["jpeg_buffers"] = jpeg_buffers
         return residual_compressed
@@ -116,7 +138,8 @@ class ResidualJPEGCompression(CompressionModel):
         device = next(self.parameters()).device
         jpeg_decoded = self.jpeg.decompress(compressed_data["jpeg_buffers"], device)
         decompress_result = self.residual_model.decompress(compressed_data["strings"], compressed_data["shape"])
-        x_hat_initial = jpeg_decoded + decompress_result["x_hat"]
+        H, W = jpeg_decoded.shape[-2:]  # the true size travels in the JPEG header
+        x_hat_initial = jpeg_decoded + decompress_result["x_hat"][..., :H, :W]
         with O.f16_region():  # fp16 activations under autocast (configs[4])
             refined = self.refine(x_hat_initial)
         decompress_result["x_hat"] = torch.clamp(x_hat_initial + refined, 0, 1)

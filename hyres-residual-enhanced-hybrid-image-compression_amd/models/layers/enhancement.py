@@ -109,7 +109,9 @@ class MultiScaleRefine(HipModule):
         feat = self.conv_in.hip(tape, x, act=L.ACT_PRELU, slope=self.act_in.weight)
         feat = self.se_block.hip(tape, feat)
         B, H, W = feat.B, feat.H, feat.W
-        assert H % 4 == 0 and W % 4 == 0, "MultiScaleRefine needs H, W divisible by 4"
+        # any H, W >= 4: F.interpolate(scale_factor=1/s) gives floor(H / s) rows with source scale s, and the way back
+        # is size=(H, W) with source scale floor(H / s) / H (enhancement.py:96-103), which the calls below spell out
+        assert H >= 4 and W >= 4, "MultiScaleRefine needs H, W >= 4 (its 1/4 scale would be empty)"
         multi = Node.new(B, H, W, 3 * mid, feat.device, dtype=feat.v.dtype)  # fp16 under autocast inference
 
         def scale1(tape, f):  # scale 1 (orig), written into multi[..., 0:mid]

@@ -21,6 +21,11 @@ a GPU target) decodes on the device as well (``jpeg_device.decode``: a self-sync
 bit-exact with libjpeg-turbo); the host reads the file headers only.  Everything else (CPU tensors or targets, grey
 input, ragged sizes, progressive / 4:2:0 / 4:4:4 / optimised-table / restart-marker files, batches of mixed sizes)
 keeps the host path; the default is ``host``.
+
+Second opt-in on top of the device codec: ``any_size=True`` (or HYRES_JPEG_ANY_SIZE=1) lets the device codec and the
+device decoder take every H x W, partial MCUs coded as libjpeg codes them (edge replication, dummy blocks, the true
+size in SOF0), still bit-exact with the host path.  Without the device codec it has no effect; without it ragged sizes
+keep the host path as before.
 """
 from __future__ import annotations
 
@@ -74,7 +79,7 @@ class TurboJPEGCompression(nn.Module):
     loop overlaps the host JPEG stage with the device step (src/utils/engine.py does this)."""
 
     def __init__(self, quality=25, lib_path: Optional[str] = None, workers: Optional[int] = None,
-                 device_codec: Optional[bool] = None):
+                 device_codec: Optional[bool] = None, any_size: Optional[bool] = None):
         super().__init__()
         self.quality = quality
         if device_codec is None:
@@ -83,6 +88,12 @@ class TurboJPEGCompression(nn.Module):
                 raise ValueError(f"HYRES_JPEG_CODEC={codec!r}: 'host' or 'device'")
             device_codec = codec == "device"
         self.device_codec = bool(device_codec)
+        if any_size is None:
+            flag = os.environ.get("HYRES_JPEG_ANY_SIZE", "0")
+            if flag not in ("0", "1"):
+                raise ValueError(f"HYRES_JPEG_ANY_SIZE={flag!r}: '0' or '1'")
+            any_size = flag == "1"
+        self.any_size = bool(any_size)  # read only where the device codec is on
         lib_path = lib_path or os.environ.get("HYRES_TURBOJPEG_LIB")
         if _TurboJPEG is not None:
             self.jpeg = _TurboJPEG(lib_path) if lib_path else _TurboJPEG()
@@ -109,11 +120,12 @@ class TurboJPEGCompression(nn.Module):
 
     def on_device(self, x: torch.Tensor) -> bool:
         """This input takes the device codec (else the host path, unchanged)."""
-        return self.device_codec and jpeg_device.supported(x)
+        return self.device_codec and jpeg_device.supported(x, self.any_size)
 
     def compress(self, x: torch.Tensor) -> List[io.BytesIO]:
         if self.on_device(x):
-            return [io.BytesIO(d) for d in jpeg_device.encode(x, self.quality)[1]]  # the only device-to-host copy
+            # the only device-to-host copy
+            return [io.BytesIO(d) for d in jpeg_device.encode(x, self.quality, self.any_size)[1]]
         imgs = _to_uint8_batch(x.detach().cpu())
         datas = self._map(lambda im: self.jpeg.encode(im, quality=self.quality), list(imgs))
         return [io.BytesIO(d) for d in datas]
@@ -125,7 +137,7 @@ class TurboJPEGCompression(nn.Module):
             return False
         sizes = set()
         for d in datas:
-            info = jpeg_device._parse(d)[0]
+            info = jpeg_device._parse(d, self.any_size)[0]
             if info is None:
                 return False
             sizes.add((info.H, info.W))
@@ -135,7 +147,7 @@ class TurboJPEGCompression(nn.Module):
         if self.device_codec:
             datas = [b.getvalue() for b in compressed_buffers]
             if self.decode_on_device(datas, device):
-                return jpeg_device.decode(datas, device)  # the host reads the file headers only
+                return jpeg_device.decode(datas, device, any_size=self.any_size)  # the host reads the headers only
         arrs = self._map(lambda b: self.jpeg.decode(b.getvalue()), list(compressed_buffers))
         return self._stack(arrs).to(device)
 
@@ -179,7 +191,7 @@ class TurboJPEGCompression(nn.Module):
         stay in flight (oldest dropped first); prefetching a batch that is already pending is a no-op."""
         if x.device.type != "cpu":
             return
-        if self.device_codec and torch.cuda.is_available() and jpeg_device.supported_shape(x):
+        if self.device_codec and torch.cuda.is_available() and jpeg_device.supported_shape(x, self.any_size):
             return  # the device codec codes this batch on the GPU: no host work to start
         key = self._key(x)
         if key in self._pending:
@@ -196,7 +208,7 @@ class TurboJPEGCompression(nn.Module):
         """(decoded [N,3,H,W] on x.device, jpeg_bpp = total bytes * 8 / (N*H*W))  (:62-77); with the device codec
         on a supported GPU tensor ``jpeg_bpp`` is a 0-dim device tensor and nothing leaves the GPU."""
         if self.on_device(x):
-            decoded, sizes = jpeg_device.roundtrip(x, self.quality)
+            decoded, sizes = jpeg_device.roundtrip(x, self.quality, self.any_size)
             return decoded, jpeg_device.bpp(sizes, x)
         device = x.device
         ent = self._pending.pop(self._key(x), None) if x.device.type == "cpu" else None

@@ -58,9 +58,7 @@ def _save(t, path):
 def process_image(model, img_path, output_dir, device, save_components=False):
     """src/inference.py:53-150: compress -> decompress, bpp from the real strings (rANS + JPEG bytes)."""
     x = _load_image(img_path)
-    H, W = x.shape[-2:]
-    if H % 32 or W % 32:
-        raise ValueError(f"{img_path}: H and W must be multiples of 32 (g_a /8 then h_a /4)")
+    H, W = x.shape[-2:]  # any size: the model pads the residual to multiples of 32, the JPEG keeps H x W
     num_pixels = x.size(0) * H * W
     x = x.to(device)
     out_enc = model.compress(x)

@@ -369,6 +369,13 @@ int hyres_accumulate(const void* x, void* y, long long n, int f16, hyres_stream_
  * io: HYRES_IO_X16 = x fp16, HYRES_IO_Y16 = y fp16, 0 = both fp32 */
 int hyres_add2d(const void* x, int ldx, void* y, int ldy, long long P, int C, int accumulate, int io,
                 hyres_stream_t s);
+/* NHWC x [B][Hs][Ws][C] (pixel stride ldx) -> y [B][Hd][Wd][C] (ldy), both anchored at the top-left corner:
+ * y[b][h][w][c] (+)= h < Hs && w < Ws ? x[b][h][w][c] : 0. Hd >= Hs, Wd >= Ws is a zero pad at the bottom and
+ * right, Hd <= Hs, Wd <= Ws the crop that is its gradient (and the other way round); accumulate: gradient fan-in
+ * (outside the source y keeps its value). io as hyres_add2d. ResidualJPEGCompression pads the residual of an
+ * image whose sides are not multiples of the transforms' stride with it and crops residual_hat back. */
+int hyres_pad2d(const void* x, int ldx, int Hs, int Ws, void* y, int ldy, int Hd, int Wd, int B, int C,
+                int accumulate, int io, hyres_stream_t s);
 /* y = a * b elementwise (in-place allowed: CheckboardMaskedConv2d's weight.data *= mask) */
 int hyres_mul(const float* a, const float* b, float* y, long long n, hyres_stream_t s);
 /* stream-ordered memset 0 (hipMemsetAsync) */
@@ -755,6 +762,36 @@ int hyres_jpeg_decode_host(const unsigned char* scans, const long long* scan_off
                            const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
                            int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
                            hyres_stream_t s);
+
+/* Any H x W (1 <= H, W < 65536): the *_any twins of the entry points above take the same arguments and run the
+ * same kernels with the same properties (device pointers, kernels on ``s`` only, no host sync, allocation or copy,
+ * grids a function of the shape alone: capture-legal), for images that are not whole 16x8 MCUs as well, still
+ * bit-exact with libjpeg-turbo. The file carries the true H x W in SOF0 and ceil(H/8) * ceil(W/16) MCUs of
+ * Y0 Y1 Cb Cr. Encode: each component's last real row / sample is replicated down / to the right before the
+ * transform (for chroma: before the h2v1 average); when ceil(W/8) is odd the last MCU's second luminance block is a
+ * dummy block (AC zero, DC = the quantised DC of the block before it). Decode: every block of the scan is decoded
+ * (status bit 4 counts the ragged grid), samples outside H x W are dropped, fancy upsampling puts its last-column
+ * rule at chroma column ceil(W/2) - 1, and a chroma row of one or two samples (W <= 4) is replicated as libjpeg
+ * does. The u8 planes and coefficients in the workspace have the padded extents; decoded [B,3,H,W] the true ones.
+ * The strict entry points keep refusing such shapes and files; on whole MCUs both run the same code. */
+long long hyres_jpeg_workspace_bytes_any(int B, int H, int W);
+long long hyres_jpeg_stream_bytes_any(int H, int W);
+int hyres_jpeg_roundtrip_any(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                             unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                             hyres_stream_t s);
+int hyres_jpeg_roundtrip_any_host(const float* x, int B, int H, int W, int quality, float* decoded, int* sizes,
+                                  unsigned char* files, long long file_stride, void* ws, long long ws_bytes,
+                                  hyres_stream_t s);
+int hyres_jpeg_parse_any(const unsigned char* file, long long nbytes, hyres_jpeg_info* info);
+long long hyres_jpeg_decode_any_workspace_bytes(int B, int H, int W, long long scan_capacity);
+int hyres_jpeg_decode_any(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                          const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                          int block_threads, float* decoded, int* status, int* rounds, void* ws, long long ws_bytes,
+                          hyres_stream_t s);
+int hyres_jpeg_decode_any_host(const unsigned char* scans, const long long* scan_off, const int* scan_len,
+                               const unsigned char* qtabs, int B, int H, int W, long long scan_capacity, int sub_bits,
+                               int block_threads, float* decoded, int* status, int* rounds, void* ws,
+                               long long ws_bytes, hyres_stream_t s);
 
 /* ------------------------------------------------------------------------------------------ */
 /* MS-SSIM / SSIM metric: pytorch_msssim's ms_ssim at its defaults (11-tap sigma-1.5 window, valid filtering,     */

@@ -14,6 +14,9 @@ call between two HIP events on an otherwise idle stream (the events see the host
 it).  Reads nothing outside the repository.  Writes ``--out`` (default profiles/jpeg_decode.json) and stdout.
 
     python scripts/jpeg_decode_bench.py [--out profiles/jpeg_decode.json]
+
+``--shape B H W`` (repeatable), ``--qualities``, ``--contents`` and ``--no-sweep`` narrow the run; a shape that is
+not whole 16x8 MCUs is coded and decoded through the any-size entry points (``any_size=True``).
 """
 import argparse
 import io
@@ -66,6 +69,10 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-model", action="store_true")
+    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--shape", type=int, nargs=3, action="append", default=None, metavar=("B", "H", "W"))
+    ap.add_argument("--qualities", type=int, nargs="+", default=[1, 50, 95])
+    ap.add_argument("--contents", nargs="+", default=["kodak_crop_tiled", "noise"])
     args = ap.parse_args()
     assert args.iters >= 50, "--iters: at least 50 calls"
 
@@ -78,25 +85,28 @@ def main():
     devc = TurboJPEGCompression(device_codec=True)
     res = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "warmup": args.warmup,
            "host_threads": host.workers, "backend": host.backend, "decompress": [], "sweep": []}
-    shapes = ((1, 512, 768), (16, 256, 256))
+    shapes = tuple(map(tuple, args.shape)) if args.shape else ((1, 512, 768), (16, 256, 256))
     for B, H, W in shapes:
-        for kind in ("kodak_crop_tiled", "noise"):
+        ragged = H % 8 != 0 or W % 16 != 0
+        kw = {"any_size": True} if ragged else {}
+        devc = TurboJPEGCompression(device_codec=True, **kw)
+        for kind in args.contents:
             x = content(kind, B, H, W).to(dev)
-            for q in (1, 50, 95):
-                files = jpeg_device.encode(x, q)[1]
+            for q in args.qualities:
+                files = jpeg_device.encode(x, q, **kw)[1]
                 bufs = [io.BytesIO(f) for f in files]
                 assert devc.decode_on_device(files, dev)
                 d, h = devc.decompress(bufs, dev), host.decompress(bufs, dev)
-                r = {"batch": [B, 3, H, W], "content": kind, "quality": q,
+                r = {"batch": [B, 3, H, W], "any_size": ragged, "content": kind, "quality": q,
                      "bytes_per_image": round(sum(map(len, files)) / B, 1), "equal": bool(torch.equal(d, h)),
                      "device": timed(lambda: devc.decompress(bufs, dev), args.iters, args.warmup),
                      "host": timed(lambda: host.decompress(bufs, dev), args.iters, args.warmup)}
-                st = jpeg_device.stage(files, dev)
+                st = jpeg_device.stage(files, dev, **kw)
                 r["device_kernels_only"] = timed(lambda: jpeg_device.decode_tensors(st), args.iters, args.warmup)
                 r["speedup"] = round(r["host"]["median_ms"] / r["device"]["median_ms"], 2)
                 res["decompress"].append(r)
                 print(json.dumps(r), flush=True)
-                if kind == "kodak_crop_tiled" or q == 95:
+                if not args.no_sweep and (kind == "kodak_crop_tiled" or q == 95):
                     for sub_bits in (256, 512, 1024, 2048):
                         for threads in (128, 256, 512, 1024):
                             t = timed(lambda: jpeg_device.decode_tensors(st, sub_bits, threads), args.iters, args.warmup)

@@ -5,7 +5,8 @@
 //       -I hyres-residual-enhanced-hybrid-image-compression_amd/csrc scripts/jpeg_decode_fuzz.cpp -o jpeg_decode_fuzz
 //   ./jpeg_decode_fuzz
 //
-// It writes files with roundtrip_image_host at three sizes and four qualities, checks that each decodes back to the
+// It writes files with roundtrip_image_host at three whole-MCU sizes and two ragged ones (13 x 21, 33 x 47: edge
+// replication, dummy blocks, an odd width; parsed as the any-size entry points parse) and four qualities, checks that each decodes back to the
 // round trip's own pixels, and then decodes every file after deterministic mutations (truncation at 64 evenly
 // spaced lengths, with and without a trailing EOI, and 256 single-bit flips chosen by an LCG) at sub_bits 32 and the
 // default.  A mutated file may decode or be refused; it must not touch memory outside its buffers.  Prints the
@@ -26,9 +27,9 @@ struct Counts {
 };
 
 // parse + decode one file exactly as the library's host twin does; returns the status or -1 when the parser refuses
-static int decode_file(const std::vector<uint8_t>& f, int sub_bits, std::vector<float>& out, Counts& n) {
+static int decode_file(const std::vector<uint8_t>& f, int sub_bits, bool any_size, std::vector<float>& out, Counts& n) {
     FileInfo fi{};
-    if (parse_file(f.data(), f.size(), &fi)) {
+    if (parse_file(f.data(), f.size(), &fi, any_size)) {
         ++n.refused;
         return -1;
     }
@@ -48,7 +49,7 @@ static int decode_file(const std::vector<uint8_t>& f, int sub_bits, std::vector<
 }
 
 int main() {
-    const int sizes[3][2] = {{8, 16}, {24, 48}, {64, 128}};
+    const int sizes[5][2] = {{8, 16}, {24, 48}, {64, 128}, {13, 21}, {33, 47}};
     const int qualities[4] = {1, 25, 50, 95};
     const int subs[2] = {32, kDefaultSubBits};
     Counts n;
@@ -57,6 +58,7 @@ int main() {
     for (const auto& hw : sizes)
         for (int q : qualities) {
             const int H = hw[0], W = hw[1];
+            const bool any = !whole_mcus(H, W);
             std::vector<float> x((size_t)3 * H * W), dec(x.size());
             for (size_t i = 0; i < x.size(); ++i) {  // noise over a ramp: long and short code words, some 0xFF bytes
                 const float ramp = (float)(i % (size_t)W) / (float)W;
@@ -65,7 +67,7 @@ int main() {
             std::vector<uint8_t> file;
             roundtrip_image_host(x.data(), H, W, q, dec.data(), &file);
             for (int sb : subs) {
-                if (decode_file(file, sb, out, n) != 0 || std::memcmp(out.data(), dec.data(), dec.size() * 4)) {
+                if (decode_file(file, sb, any, out, n) != 0 || std::memcmp(out.data(), dec.data(), dec.size() * 4)) {
                     std::printf("%dx%d q%d sub_bits %d: the unmutated file does not decode to the round trip\n", H, W,
                                 q, sb);
                     return 1;
@@ -73,17 +75,17 @@ int main() {
                 for (int t = 0; t < 64; ++t) {  // truncation, as it is and closed with an EOI
                     const size_t len = file.size() * (size_t)t / 64;
                     std::vector<uint8_t> cut(file.begin(), file.begin() + (long)len);
-                    decode_file(cut, sb, out, n);
+                    decode_file(cut, sb, any, out, n);
                     cut.push_back(0xFF);
                     cut.push_back(0xD9);
-                    decode_file(cut, sb, out, n);
+                    decode_file(cut, sb, any, out, n);
                 }
                 uint32_t s = 99u + (uint32_t)(H * 131 + q);
                 for (int t = 0; t < 256; ++t) {  // one flipped bit anywhere after the SOI
                     std::vector<uint8_t> m = file;
                     const size_t bit = 16 + (size_t)(lcg(s) >> 4) % ((file.size() - 2) * 8);
                     m[bit >> 3] ^= (uint8_t)(0x80u >> (bit & 7));
-                    decode_file(m, sb, out, n);
+                    decode_file(m, sb, any, out, n);
                 }
             }
         }

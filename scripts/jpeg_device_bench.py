@@ -11,6 +11,10 @@ The device round trip must be at least ``--min-speedup`` (5) times faster than t
 else the script exits 1.  The result goes to ``--out`` (default profiles/jpeg_device.json) and to stdout.
 
     python scripts/jpeg_device_bench.py [--out profiles/jpeg_device.json]
+
+``--shape B H W`` times another batch; one that is not whole 16x8 MCUs goes through the any-size entry points
+(``any_size=True``, also forced by ``--any-size``) and is compared with the host stage's Pillow path on the same
+bytes.  The graphed loop needs sides that are multiples of 32 and is skipped otherwise.
 """
 import argparse
 import json
@@ -57,6 +61,8 @@ def main():
     ap.add_argument("--loop-steps", type=int, nargs=2, default=[8, 40])
     ap.add_argument("--min-speedup", type=float, default=5.0)
     ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--shape", type=int, nargs=3, default=None, metavar=("B", "H", "W"))
+    ap.add_argument("--any-size", action="store_true")
     args = ap.parse_args()
 
     from hyres_hip import jpeg_host
@@ -67,16 +73,20 @@ def main():
     from models.utils.turbo_jpeg_compression import TurboJPEGCompression
     assert torch.cuda.is_available(), "this benchmark needs the GPU"
     dev = torch.device("cuda:0")
-    B, S = args.batch, args.size
-    x_cpu = torch.randint(0, 256, (B, 3, S, S), generator=torch.Generator().manual_seed(1)).float() / 255.0
+    B, H, W = args.shape if args.shape else (args.batch, args.size, args.size)
+    any_size = args.any_size or H % 8 != 0 or W % 16 != 0
+    kw = {"any_size": True} if any_size else {}
+    if H % 32 or W % 32:
+        args.no_loop = True
+    x_cpu = torch.randint(0, 256, (B, 3, H, W), generator=torch.Generator().manual_seed(1)).float() / 255.0
     x = x_cpu.to(dev)
-    res = {"batch": [B, 3, S, S], "data": "uniform 8-bit noise", "iters": args.iters, "host_procs": nprocs,
+    res = {"batch": [B, 3, H, W], "any_size": any_size, "data": "uniform 8-bit noise", "iters": args.iters, "host_procs": nprocs,
            "device": torch.cuda.get_device_name(0)}
 
     for q in (1, 50):
         r = {}
         for tag, fn in (("roundtrip", jpeg_device.roundtrip), ("roundtrip_with_files", jpeg_device._run)):
-            call = (lambda: fn(x, q)) if tag == "roundtrip" else (lambda: fn(x, q, True))
+            call = (lambda: fn(x, q, **kw)) if tag == "roundtrip" else (lambda: fn(x, q, True, **kw))
             for _ in range(args.warmup):
                 call()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -93,7 +103,7 @@ def main():
         for _ in range(5):
             j(x_cpu)
         r["host_pool_roundtrip_ms"] = round((time.perf_counter() - t0) * 1000 / 5, 3)
-        dec_d, sizes = jpeg_device.roundtrip(x, q)
+        dec_d, sizes = jpeg_device.roundtrip(x, q, **kw)
         r["equal_to_host"] = bool(torch.equal(dec_d.cpu(), dec_h)) and float(jpeg_device.bpp(sizes, x)) == float(
             torch.tensor(bpp_h, dtype=torch.float32))
         r["bytes_per_image"] = round(float(sizes.sum()) / B, 1)
