@@ -2320,6 +2320,27 @@ static ConvRoute route(const hyres_conv_geom* g, const hyres_epilogue* e, const 
     return r;
 }
 
+// ConvFacts of a launch from its real operands: only the pointers' alignment is read, never what they point to
+static ConvFacts conv_facts(const hyres_conv_geom* g, const hyres_epilogue* e, const void* x, const void* w2, int ldw,
+                            const void* y, const void* ws, long long ws_bytes) {
+    ConvFacts f;
+    f.xw16 = aligned16(x) && aligned16(w2) && g->ldx % 4 == 0 && ldw % 4 == 0;
+    {
+        auto al = [](const void* p, int ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); };
+        // HYRES_EPI_SA_BWD reads aux0 ([P][2]) and aux2 (argmax), HYRES_EPI_ROWSCALE aux1 (the scale), one scalar per
+        // pixel: no alignment needed
+        const bool sa = e->kind == HYRES_EPI_SA_BWD, rs = e->kind == HYRES_EPI_ROWSCALE;
+        f.vec4 = g->Co % 4 == 0 && al(y, g->ldy) && al(e->bias, 4) && al(e->res, e->ldres) && al(e->out2, e->ldo2) &&
+                 (sa || al(e->aux0, e->ld0)) && (rs || al(e->aux1, e->ld1)) && (sa || al(e->aux2, e->ld2));
+    }
+    f.rsrc_ok = epi_span_ok(g, e);
+    f.y8 = aligned8(y);
+    f.opnd8 = aligned8(e->res) && aligned8(e->aux0) && aligned8(e->out2);
+    f.ws_bytes = ws ? ws_bytes : 0;
+    f.ws16 = aligned16(ws);
+    return f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
@@ -2440,21 +2461,7 @@ int hyres_conv_forward(const hyres_conv_geom* g, const float* x, const float* w2
     HY_REQUIRE(g && x && w2 && y && e, HYRES_E_ARG, "conv_forward: NULL argument");
     HY_REQUIRE(g->nphase >= 1 && g->nphase <= 4 && g->Ci > 0 && g->Co > 0, HYRES_E_SHAPE, "conv: bad geom");
     HY_REQUIRE(ldw >= g->ntaps * g->Ci, HYRES_E_SHAPE, "conv: ldw %d < ntaps*Ci %d", ldw, g->ntaps * g->Ci);
-    ConvFacts f;
-    f.xw16 = aligned16(x) && aligned16(w2) && g->ldx % 4 == 0 && ldw % 4 == 0;
-    {
-        auto al = [](const void* p, int ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); };
-        // HYRES_EPI_SA_BWD reads aux0 ([P][2]) and aux2 (argmax), HYRES_EPI_ROWSCALE aux1 (the scale), one scalar per
-        // pixel: no alignment needed
-        const bool sa = e->kind == HYRES_EPI_SA_BWD, rs = e->kind == HYRES_EPI_ROWSCALE;
-        f.vec4 = g->Co % 4 == 0 && al(y, g->ldy) && al(e->bias, 4) && al(e->res, e->ldres) && al(e->out2, e->ldo2) &&
-                 (sa || al(e->aux0, e->ld0)) && (rs || al(e->aux1, e->ld1)) && (sa || al(e->aux2, e->ld2));
-    }
-    f.rsrc_ok = epi_span_ok(g, e);
-    f.y8 = aligned8(y);
-    f.opnd8 = aligned8(e->res) && aligned8(e->aux0) && aligned8(e->out2);
-    f.ws_bytes = ws ? ws_bytes : 0;
-    f.ws16 = aligned16(ws);
+    const ConvFacts f = conv_facts(g, e, x, w2, ldw, y, ws, ws_bytes);
     const ConvRoute r = route(g, e, f);
     const int mode = r.mode;
     ConvArgs a;
@@ -2542,10 +2549,10 @@ int hyres_conv_forward(const hyres_conv_geom* g, const float* x, const float* w2
     return launch_tiles(a, r, st);
 }
 
-int hyres_conv_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, int split, char* buf, int n) {
-    HY_REQUIRE(g && e && buf && n > 0, HYRES_E_ARG, "conv_kernel_name: bad args");
+// the kernel of route r as rocprof prints it (split: the split-K instantiation of the tiles)
+static void conv_route_name(const hyres_conv_geom* g, const hyres_epilogue* e, const ConvRoute& r, bool split, char* buf,
+                            int n) {
     static const char* tiles[5] = {"2, 2, 2, 2", "2, 1, 2, 2", "1, 1, 4, 1", "1, 2, 2, 2", "1, 1, 2, 2"};
-    const ConvRoute r = route(g, e, ConvFacts::ideal());
     const int nt = cfg_nt(r.cfg), k = cfg_k(r.cfg), f = cfg_f(r.cfg), io = e->io_f16 & 3;
     const char* sp = split ? "true" : "false";
     switch (r.family) {
@@ -2580,6 +2587,26 @@ int hyres_conv_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, in
                              r.gemm == ConvGemm::F16 ? "true" : "false");
             }
     }
+}
+
+int hyres_conv_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, int split, char* buf, int n) {
+    HY_REQUIRE(g && e && buf && n > 0, HYRES_E_ARG, "conv_kernel_name: bad args");
+    conv_route_name(g, e, route(g, e, ConvFacts::ideal()), split != 0, buf, n);
+    return 0;
+}
+
+int hyres_conv_kernel_name_at(const hyres_conv_geom* g, const hyres_epilogue* e, const void* x, const void* w2, int ldw,
+                              const void* y, const void* ws, long long ws_bytes, int* vec4, char* buf, int n) {
+    HY_REQUIRE(g && e && buf && n > 0, HYRES_E_ARG, "conv_kernel_name_at: bad args");
+    const ConvRoute r = route(g, e, conv_facts(g, e, x, w2, ldw, y, ws, ws_bytes));
+    const bool split = r.family == ConvFamily::TILES && r.nsplit > 1;
+    conv_route_name(g, e, r, split, buf, n);
+    if (split) {  // launch_tiles' second kernel
+        const size_t len = strlen(buf);
+        snprintf(buf + len, n - len, "+%s<%s>", r.vec4 ? "conv_splitk_reduce4_kernel" : "conv_splitk_reduce_kernel",
+                 (e->io_f16 & 2) ? "true" : "false");
+    }
+    if (vec4) *vec4 = r.vec4;
     return 0;
 }
 

@@ -163,6 +163,14 @@ long long hyres_conv_workspace_bytes(const hyres_conv_geom* g);
  * "conv_fwd_kernel<2, 1, 2, 2, 0, false, false>" (16B-aligned operands assumed).  Host-only, no
  * launch: the profiling label of bench.py's roofline line comes from the launcher's own choice. */
 int hyres_conv_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, int split, char* buf, int n);
+/* The same for the launch hyres_conv_forward would make with these operands: the route sees their real alignment
+ * (x, w2, y, the epilogue's pointers, the workspace), ldw and the workspace size, and says itself whether it splits K.
+ * A split launch is named "<tiles kernel>+conv_splitk_reduce4_kernel<Y fp16>" or "...+conv_splitk_reduce_kernel<...>",
+ * whichever reduce follows. *vec4 (may be NULL) gets the route's float4-epilogue flag. Host-only: no launch, no device
+ * access, the pointers are never dereferenced. */
+int hyres_conv_kernel_name_at(const hyres_conv_geom* g, const hyres_epilogue* e, const void* x, const void* w2,
+                              int ldw, const void* y, const void* ws, long long ws_bytes,
+                              int* vec4, char* buf, int n);
 /* Tuning override of the conv planners (sweeps only; not used by the product path). key 0: tile
  * (0 = 128x128, 1 = 128x64, 2 = 128x32, 3 = 64x128, 4 = 64x64), 1: split-K target block count,
  * 2: minimum K chunks per split; value -1 restores the built-in heuristic. *old (may be NULL) gets the
