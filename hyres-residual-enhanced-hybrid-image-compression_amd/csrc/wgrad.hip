@@ -383,23 +383,17 @@ __global__ __launch_bounds__(256 * G) void wgrad1x1_kernel(const WgradArgs a) {
     float bsum[TM];
 #pragma unroll
     for (int i = 0; i < TM; ++i) bsum[i] = 0.f;
-    // the block's chunks [kb0, ke0), this group's contiguous share [kb, ke); every group runs `iters` barrier
-    // steps (a group with fewer chunks idles through its last one)
-    const int kb0 = split * a.chunks_per_split;
-    const int ke0 = min(a.nchunks, kb0 + a.chunks_per_split);
-    const int share = (max(ke0 - kb0, 0) + G - 1) / G;
-    const int kb = min(ke0, kb0 + grp * share), ke = min(ke0, kb + share);
-    const int iters = share;
-    if (kb < ke) {
-        load(kb);
+    const GroupShare gs = group_share<G>(a, split, grp);
+    if (gs.kb < gs.ke) {
+        load(gs.kb);
         store(0);
     }
     __syncthreads();
     int cur = 0;
-    for (int it = 0; it < iters; ++it) {
-        const int kc = kb + it;
-        const bool live = kc < ke;
-        const bool next = kc + 1 < ke;
+    for (int it = 0; it < gs.share; ++it) {
+        const int kc = gs.kb + it;
+        const bool live = kc < gs.ke;
+        const bool next = kc + 1 < gs.ke;
         if (next) load(kc + 1);  // in flight during this chunk's MFMAs
         if (live) {
             const float* Ps = Psm + cur * (KT * PP);
@@ -479,12 +473,7 @@ __global__ __launch_bounds__(256 * G) void wgrad1x1_kernel(const WgradArgs a) {
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn) {
             const int n = n0 + wn * TN * 32 + tn * 32 + lr;
-            if (n >= d.N) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < d.M) out[(long long)m * d.N + n] = acc[tm][tn][r];
-            }
+            if (n < d.N) slab_store_acc(acc[tm][tn], out + n, m0 + wm * TM * 32 + tm * 32, lh, d.M, d.N);
         }
 }
 
@@ -537,12 +526,8 @@ template <int KR, int KW, int SQ, int DIL = 1, int G = 1>
 __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(const WgradArgs a, int dhg, int dwg) {
     // DIL: tap spacing (2: MultiScaleRefine's dilated 3x3, enhancement.py:44-51): the KR halo rows are DIL
     // rows apart, the halo columns span 31*SQ + DIL*(KW-1) + 1 pixels
-    constexpr int BM = 64, BN = 64, NT = KR * KW, HC = 31 * SQ + DIL * (KW - 1) + 1;  // halo columns of a 32-px chunk
-    constexpr int PP = BM + 4, PQ = BN + 4;
-    constexpr int PSZ = KT * PP, HSZ = KR * HC * PQ;
-    constexpr int P_V = KT * BM / 4 / 256;
-    constexpr int H_E = KR * HC * (BN / 4);
-    constexpr int H_V = (H_E + 255) / 256;
+    using T = HaloTile<KR, KW, SQ, DIL, 4>;
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, HC = T::HC, PP = T::PP, PQ = T::PQ, PSZ = T::PSZ, HSZ = T::HSZ;
     __shared__ __attribute__((aligned(16))) float smem_all[G * 2 * (PSZ + HSZ)];
     const hyres_wgrad_desc& d = a.d;
     const int tid = threadIdx.x & 255, gq = threadIdx.x >> 8;
@@ -554,28 +539,19 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(con
     const int t0 = grp * NT;
     const int dh0 = dhg + grp * KR * DIL;  // the group's first kernel row offset, first column offset dwg
     const int cpr = d.Wq / 32;
-    float4 rp[P_V], rh[H_V];
+    float4 rp[T::P_V], rh[T::H_V];
     auto load = [&](int kc) {
-        const int b = kc / (d.Hq * cpr);
-        const int rem = kc - b * d.Hq * cpr;
-        const int i = rem / cpr;
-        const int j0 = (rem - i * cpr) * 32;
-        const long long q0 = (long long)kc * 32;
+        const HaloChunk ch = halo_chunk(d, cpr, kc);
 #pragma unroll
-        for (int q = 0; q < P_V; ++q) {
+        for (int q = 0; q < T::P_V; ++q) {
             const int e = tid + 256 * q;
             const int row = e / (BM / 4), c = (e % (BM / 4)) * 4;
-            rp[q] = m0 + c < d.M ? ld4(a.p + (q0 + row) * d.ldp + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            rp[q] = m0 + c < d.M ? ld4(a.p + (ch.q0 + row) * d.ldp + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
-        for (int q = 0; q < H_V; ++q) {
-            const int e = tid + 256 * q;
-            const int pix = e / (BN / 4), c = (e % (BN / 4)) * 4;
-            const int hr = pix / HC, hc = pix - (pix / HC) * HC;
-            const int ih = i * SQ + dh0 + DIL * hr, iw = j0 * SQ + dwg + hc;
-            const bool ok = e < H_E && (unsigned)ih < (unsigned)d.Hqq && (unsigned)iw < (unsigned)d.Wqq && n0 + c < d.N;
-            rh[q] = ok ? ld4(a.q + ((long long)(b * d.Hqq + ih) * d.Wqq + iw) * d.ldq + n0 + c)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < T::H_V; ++q) {
+            const HaloElem he = halo_elem<T>(d, tid + 256 * q, ch, dh0, dwg, n0);
+            rh[q] = he.ok ? ld4(a.q + he.off) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     // bias gradient = column sums of P, accumulated from the staging registers (this thread's channel
@@ -587,15 +563,15 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(con
         float* Ps = smem + buf * (PSZ + HSZ);
         float* Hs = Ps + PSZ;
 #pragma unroll
-        for (int q = 0; q < P_V; ++q) {
+        for (int q = 0; q < T::P_V; ++q) {
             const int e = tid + 256 * q;
             if (do_bias) { bsum.x += rp[q].x; bsum.y += rp[q].y; bsum.z += rp[q].z; bsum.w += rp[q].w; }
             *reinterpret_cast<float4*>(&Ps[(e / (BM / 4)) * PP + (e % (BM / 4)) * 4]) = rp[q];
         }
 #pragma unroll
-        for (int q = 0; q < H_V; ++q) {
+        for (int q = 0; q < T::H_V; ++q) {
             const int e = tid + 256 * q;
-            if (e < H_E) *reinterpret_cast<float4*>(&Hs[(e / (BN / 4)) * PQ + (e % (BN / 4)) * 4]) = rh[q];
+            if (e < T::H_E) *reinterpret_cast<float4*>(&Hs[(e / (BN / 4)) * PQ + (e % (BN / 4)) * 4]) = rh[q];
         }
     };
 
@@ -607,23 +583,18 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(con
     for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    // the split's chunks [kb0, ke0), this group's contiguous share [kb, ke); every group runs `iters` barrier
-    // steps (a group with fewer chunks idles through its last ones)
-    const int kb0 = split * a.chunks_per_split;
-    const int ke0 = min(a.nchunks, kb0 + a.chunks_per_split);
-    const int share = (max(ke0 - kb0, 0) + G - 1) / G;
-    const int kb = min(ke0, kb0 + gq * share), ke = min(ke0, kb + share);
-    if (kb < ke) {
-        load(kb);
+    const GroupShare gs = group_share<G>(a, split, gq);
+    if (gs.kb < gs.ke) {
+        load(gs.kb);
         store(0);
     }
     __syncthreads();
     int cur = 0;
-    for (int it = 0; it < share; ++it) {
-        const int kc = kb + it;
-        const bool next = kc + 1 < ke;
+    for (int it = 0; it < gs.share; ++it) {
+        const int kc = gs.kb + it;
+        const bool next = kc + 1 < gs.ke;
         if (next) load(kc + 1);  // next chunk in flight during this chunk's NT x 16 MFMAs
-        if (kc < ke) {
+        if (kc < gs.ke) {
             const float* Ps = smem + cur * (PSZ + HSZ);
             const float* Hs = Ps + PSZ;
             static_for<NT>([&](auto J) {
@@ -643,35 +614,14 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_kernel(con
         cur ^= 1;
     }
     if (do_bias) {  // block-uniform
-        float4* red = reinterpret_cast<float4*>(smem_all);  // the loop ended with a barrier
-        red[threadIdx.x] = bsum;
-        __syncthreads();
-        if (threadIdx.x < BM / 4) {
-            float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int r = 0; r < 256 * G / (BM / 4); ++r) {
-                const float4 v = red[threadIdx.x + r * (BM / 4)];
-                s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w;
-            }
-            float* dst = a.bias_slab + (long long)split * d.M + m0 + 4 * tid;
-            const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
-            for (int c = 0; c < 4; ++c)
-                if (m0 + 4 * tid + c < d.M) dst[c] = sv[c];
-        }
+        bias_block_reduce<BM, 256 * G>(reinterpret_cast<float4*>(smem_all), bsum, a.bias_slab, split, m0, d.M);
         __syncthreads();
     }
     if constexpr (G > 1) {
         combine_groups<NT, G, G * 2 * (PSZ + HSZ)>(acc, smem_all, tid, gq);
         if (gq != 0) return;
     }
-    const long long MN = (long long)d.M * d.N;
-    static_for<NT>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const int n = n0 + wn * 32 + lr;
-        if (n < d.N) {
-            float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
-        }
-    });
+    slab_store_taps<NT>(acc, a, split, t0, m0 + wm * 32, n0 + wn * 32 + lr, lh);
 }
 
 
@@ -823,6 +773,8 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const WgradArgs a) {
 
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    // tr_lane, bias_block_reduce and slab_store_acc stay written out here: with them the 1x1 fp16 gradient (B16 128^2
+    // 64 -> 128, bias) took 36.9 - 37.0 us against the parent's 36.8 - 36.8 us, past the parent's own spread
     // transposed-read address of this lane: half h = lane>>5 takes k rows 8h..8h+7 of each 16-k step; in
     // its 16-lane group g, lane 4q+p supplies row (.. + q), columns 16g + 4p .. +3
     const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
@@ -940,12 +892,9 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const WgradArgs a) {
 template <int KR, int KW, int SQ, int DIL = 1, int IOH = 0, int G = 1>  // G: as wgrad_halo_kernel
 __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel(const WgradArgs a, int dhg, int dwg) {
     constexpr bool PH = (IOH & 1) != 0, QH = (IOH & 2) != 0;  // fp16 operands in HBM (wgrad_f16_kernel)
-    constexpr int BM = 64, BN = 64, NT = KR * KW, HC = 31 * SQ + DIL * (KW - 1) + 1;
-    constexpr int PP = BM + 32, PQ = BN + 32;  // halves
-    constexpr int PSZ = KT * PP, HSZ = KR * HC * PQ;
-    constexpr int P_V = KT * BM / 4 / 256;  // 2 float4 of P per thread and chunk
-    constexpr int H_E = KR * HC * (BN / 4);
-    constexpr int H_V = (H_E + 255) / 256;
+    using T = HaloTile<KR, KW, SQ, DIL, 32>;  // pitches in halves
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, HC = T::HC, PP = T::PP, PQ = T::PQ, PSZ = T::PSZ, HSZ = T::HSZ;
+    constexpr int P_V = T::P_V, H_E = T::H_E, H_V = T::H_V;
     static_assert((PSZ + HSZ) % 4 == 0, "8-byte aligned buffers for the transposed reads");
     __shared__ __attribute__((aligned(16))) _Float16 smem_all[G * 2 * (PSZ + HSZ)];
     const hyres_wgrad_desc& d = a.d;
@@ -962,15 +911,14 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel
     const int pc = (tid % (BM / 4)) * 4, prow0 = tid / (BM / 4);
     quad_t<PH> rp[P_V];
     quad_t<QH> rh[H_V];
+    // halo_elem and bias_block_reduce stay written out here: with them the dilated 3x3 (B16 128^2 64 -> 64) took
+    // 58.4 - 58.9 us against the parent's 57.2 - 57.8 us, past the parent's own spread
     auto load = [&](int kc) {
-        const int b = kc / (d.Hq * cpr);
-        const int rem = kc - b * d.Hq * cpr;
-        const int i = rem / cpr;
-        const int j0 = (rem - i * cpr) * 32;
-        const long long q0 = (long long)kc * 32;
+        const HaloChunk ch = halo_chunk(d, cpr, kc);
+        const int b = ch.b, i = ch.i, j0 = ch.j0;
 #pragma unroll
         for (int q = 0; q < P_V; ++q)
-            rp[q] = m0 + pc < d.M ? ldq4<PH>(a.p, (q0 + prow0 + 16 * q) * d.ldp + m0 + pc) : zq4<PH>();
+            rp[q] = m0 + pc < d.M ? ldq4<PH>(a.p, (ch.q0 + prow0 + 16 * q) * d.ldp + m0 + pc) : zq4<PH>();
 #pragma unroll
         for (int q = 0; q < H_V; ++q) {
             const int e = tid + 256 * q;
@@ -1003,39 +951,34 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel
 
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    // transposed-read lane address (wgrad_f16_kernel): half lh takes k rows 8lh..8lh+7 of a 16-k step
-    const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
-    const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
+    const TrLane tl = tr_lane(lane);
     floatx16 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    const int kb0 = split * a.chunks_per_split;
-    const int ke0 = min(a.nchunks, kb0 + a.chunks_per_split);
-    const int share = (max(ke0 - kb0, 0) + G - 1) / G;
-    const int kb = min(ke0, kb0 + gq * share), ke = min(ke0, kb + share);
-    if (kb < ke) {
-        load(kb);
+    const GroupShare gs = group_share<G>(a, split, gq);
+    if (gs.kb < gs.ke) {
+        load(gs.kb);
         store(0);
     }
     __syncthreads();
     int cur = 0;
-    for (int it = 0; it < share; ++it) {
-        const int kc = kb + it;
-        const bool next = kc + 1 < ke;
+    for (int it = 0; it < gs.share; ++it) {
+        const int kc = gs.kb + it;
+        const bool next = kc + 1 < gs.ke;
         if (next) load(kc + 1);  // next chunk in flight during this chunk's NT x 2 MFMAs per wave
         const _Float16* Ps = smem + cur * (PSZ + HSZ);
         const _Float16* Hs = Ps + PSZ;
 #pragma unroll
         for (int s = 0; s < KT / 16; ++s) {
-            if (kc >= ke) break;  // this group idles through the split's last step
-            const halfx8_t af = tr_frag(Ps + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
+            if (kc >= gs.ke) break;  // this group idles through the split's last step
+            const halfx8_t af = tr_frag(Ps + (16 * s + tl.row) * PP + wm * 32 + tl.col, PP);
             static_for<NT>([&](auto J) {
                 constexpr int t = decltype(J)::value;
                 constexpr int hr = t / KW, hc = t % KW;
                 const halfx8_t bf =
-                    tr_frag(Hs + (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col, SQ * PQ);
+                    tr_frag(Hs + (hr * HC + DIL * hc + SQ * (16 * s + tl.row)) * PQ + wn * 32 + tl.col, SQ * PQ);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[t], 0, 0, 0);
             });
         }
@@ -1064,16 +1007,7 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wgrad_halo_f16_kernel
         combine_groups<NT, G, G * (PSZ + HSZ)>(acc, reinterpret_cast<float*>(smem_all), tid, gq);
         if (gq != 0) return;
     }
-    const int lr = lane & 31;
-    const long long MN = (long long)d.M * d.N;
-    static_for<NT>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const int n = n0 + wn * 32 + lr;
-        if (n < d.N) {
-            float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
-        }
-    });
+    slab_store_taps<NT>(acc, a, split, t0, m0 + wm * 32, n0 + wn * 32 + (lane & 31), tl.lh);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1132,6 +1066,8 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_kernel(const WgradArgs a) {
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    // tr_lane, bias_block_reduce and slab_store_acc stay written out here: with them the 1x1 gradient (B16 128^2
+    // 64 -> 128, bias) took 51.5 - 51.6 us against the parent's 51.2 - 51.3 us, past the parent's own spread
     const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
     const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
     floatx16 acc[TM][TN];
@@ -1278,8 +1214,7 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
-    const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
+    const TrLane tl = tr_lane(lane);
     floatx16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -1308,13 +1243,13 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
 #pragma unroll
                 for (int pl3 = 0; pl3 < 3; ++pl3)
                     af[tm][pl3] =
-                        tr_frag(Ps + pl3 * PLANE + (16 * s + tr_row) * PP + wm * TM * 32 + tm * 32 + tr_col, PP);
+                        tr_frag(Ps + pl3 * PLANE + (16 * s + tl.row) * PP + wm * TM * 32 + tm * 32 + tl.col, PP);
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
                 for (int pl3 = 0; pl3 < 3; ++pl3)
                     bf[tn][pl3] =
-                        tr_frag(Qs + pl3 * PLANE + (16 * s + tr_row) * PQ + wn * TN * 32 + tn * 32 + tr_col, PQ);
+                        tr_frag(Qs + pl3 * PLANE + (16 * s + tl.row) * PQ + wn * TN * 32 + tn * 32 + tl.col, PQ);
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -1327,6 +1262,7 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
         body(kc, 0, pA, qA, pB, qB);
         if (kc + 1 < ke) body(kc + 1, 1, pB, qB, pA, qA);
     }
+    // bias_block_reduce and slab_store_acc stay written out, as in wgrad1x1_bf6_kernel and for its reason
     if (do_bias) {  // block-uniform
         float4* red = reinterpret_cast<float4*>(smem);  // the loop ended with a barrier
         red[tid] = bsum;
@@ -1354,7 +1290,7 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
             if (n >= d.N) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int m = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * tl.lh;
                 if (m < d.M) out[(long long)m * d.N + n] = acc[tm][tn][r];
             }
         }
@@ -1371,12 +1307,9 @@ __global__ __launch_bounds__(256) void wgrad1x1_bf6_pf2_kernel(const WgradArgs a
 // ------------------------------------------------------------------------------------------------
 template <int KR, int KW, int SQ, int DIL = 1>
 __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs a, int dhg, int dwg) {
-    constexpr int BM = 64, BN = 64, NT = KR * KW, HC = 31 * SQ + DIL * (KW - 1) + 1;
-    constexpr int PP = BM + 32, PQ = BN + 32;  // bf16 row pitches (the transposed reads' conflict-free pitch)
-    constexpr int PSZ = KT * PP, HSZ = KR * HC * PQ, PLANE = PSZ + HSZ, BUF = 3 * PLANE;
-    constexpr int P_V = KT * BM / 4 / 256;
-    constexpr int H_E = KR * HC * (BN / 4);
-    constexpr int H_V = (H_E + 255) / 256;
+    using T = HaloTile<KR, KW, SQ, DIL, 32>;  // bf16 row pitches (the transposed reads' conflict-free pitch)
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, HC = T::HC, PP = T::PP, PQ = T::PQ, PSZ = T::PSZ;
+    constexpr int PLANE = PSZ + T::HSZ, BUF = 3 * PLANE;
     static_assert(PLANE % 4 == 0, "8-byte aligned planes for the transposed reads");
     static_assert(2 * BUF * 2 <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
@@ -1390,25 +1323,16 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
     const int dh0 = dhg + grp * KR * DIL;
     const int cpr = d.Wq / 32;
     const int pc = (tid % (BM / 4)) * 4, prow0 = tid / (BM / 4);  // this thread's fixed P channel quad
-    float4 rp[P_V], rh[H_V];
+    float4 rp[T::P_V], rh[T::H_V];
     auto load = [&](int kc) {
-        const int b = kc / (d.Hq * cpr);
-        const int rem = kc - b * d.Hq * cpr;
-        const int i = rem / cpr;
-        const int j0 = (rem - i * cpr) * 32;
-        const long long q0 = (long long)kc * 32;
+        const HaloChunk ch = halo_chunk(d, cpr, kc);
 #pragma unroll
-        for (int q = 0; q < P_V; ++q)
-            rp[q] = m0 + pc < d.M ? ld4(a.p + (q0 + prow0 + 16 * q) * d.ldp + m0 + pc) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < T::P_V; ++q)
+            rp[q] = m0 + pc < d.M ? ld4(a.p + (ch.q0 + prow0 + 16 * q) * d.ldp + m0 + pc) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int q = 0; q < H_V; ++q) {
-            const int e = tid + 256 * q;
-            const int pix = e / (BN / 4), c = (e % (BN / 4)) * 4;
-            const int hr = pix / HC, hc = pix - (pix / HC) * HC;
-            const int ih = i * SQ + dh0 + DIL * hr, iw = j0 * SQ + dwg + hc;
-            const bool ok = e < H_E && (unsigned)ih < (unsigned)d.Hqq && (unsigned)iw < (unsigned)d.Wqq && n0 + c < d.N;
-            rh[q] = ok ? ld4(a.q + ((long long)(b * d.Hqq + ih) * d.Wqq + iw) * d.ldq + n0 + c)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < T::H_V; ++q) {
+            const HaloElem he = halo_elem<T>(d, tid + 256 * q, ch, dh0, dwg, n0);
+            rh[q] = he.ok ? ld4(a.q + he.off) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     const bool do_bias = a.bias_slab != nullptr && nt == 0 && grp == 0;
@@ -1416,22 +1340,20 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
     auto store = [&](int buf) {
         __bf16* B0 = smem + buf * BUF;
 #pragma unroll
-        for (int q = 0; q < P_V; ++q) {
+        for (int q = 0; q < T::P_V; ++q) {
             if (do_bias) { bsum.x += rp[q].x; bsum.y += rp[q].y; bsum.z += rp[q].z; bsum.w += rp[q].w; }
             bf6_put3<PLANE>(B0, (prow0 + 16 * q) * PP + pc, rp[q]);
         }
 #pragma unroll
-        for (int q = 0; q < H_V; ++q) {
+        for (int q = 0; q < T::H_V; ++q) {
             const int e = tid + 256 * q;
-            if (e < H_E) bf6_put3<PLANE>(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
+            if (e < T::H_E) bf6_put3<PLANE>(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
         }
     };
 
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    // transposed-read lane address (wgrad_f16_kernel): half lh takes k rows 8lh..8lh+7 of a 16-k step
-    const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
-    const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
+    const TrLane tl = tr_lane(lane);
     floatx16 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -1454,11 +1376,11 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
         for (int s = 0; s < KT / 16; ++s) {
             bf16x8_t af[3];
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) af[pl] = tr_frag(Ps + pl * PLANE + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
+            for (int pl = 0; pl < 3; ++pl) af[pl] = tr_frag(Ps + pl * PLANE + (16 * s + tl.row) * PP + wm * 32 + tl.col, PP);
             static_for<NT>([&](auto J) {
                 constexpr int t = decltype(J)::value;
                 constexpr int hr = t / KW, hc = t % KW;
-                const int ob = (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col;
+                const int ob = (hr * HC + DIL * hc + SQ * (16 * s + tl.row)) * PQ + wn * 32 + tl.col;
                 bf16x8_t bf[3];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) bf[pl] = tr_frag(Hs + pl * PLANE + ob, SQ * PQ);
@@ -1469,32 +1391,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
         __syncthreads();
         cur ^= 1;
     }
-    if (do_bias) {  // block-uniform
-        float4* red = reinterpret_cast<float4*>(smem);  // the loop ended with a barrier
-        red[tid] = bsum;
-        __syncthreads();
-        if (tid < BM / 4) {
-            float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int r = 0; r < 256 / (BM / 4); ++r) {
-                const float4 v = red[tid + r * (BM / 4)];
-                s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w;
-            }
-            float* dst = a.bias_slab + (long long)split * d.M + m0 + 4 * tid;
-            const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
-            for (int c = 0; c < 4; ++c)
-                if (m0 + 4 * tid + c < d.M) dst[c] = sv[c];
-        }
-    }
-    const int lr = lane & 31;
-    const long long MN = (long long)d.M * d.N;
-    static_for<NT>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const int n = n0 + wn * 32 + lr;
-        if (n < d.N) {
-            float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
-        }
-    });
+    // block-uniform; no barrier after it: nothing writes the LDS again
+    if (do_bias) bias_block_reduce<BM, 256>(reinterpret_cast<float4*>(smem), bsum, a.bias_slab, split, m0, d.M);
+    slab_store_taps<NT>(acc, a, split, t0, m0 + wm * 32, n0 + wn * 32 + (lane & 31), tl.lh);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1509,12 +1408,10 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_bf6_kernel(const WgradArgs 
 template <int KW, int SQ, int DIL = 1, int MINB = 2>
 __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const WgradArgs a, int dhg, int dwg) {
     constexpr int KR = 1;
-    constexpr int BM = 64, BN = 64, NT = KR * KW, HC = 31 * SQ + DIL * (KW - 1) + 1;
-    constexpr int PP = BM + 32, PQ = BN + 32;
-    constexpr int PSZ = KT * PP, HSZ = KR * HC * PQ, PLANE = PSZ + HSZ, BUF = 3 * PLANE;
-    constexpr int P_V = KT * BM / 4 / 256;
-    constexpr int H_E = KR * HC * (BN / 4);
-    constexpr int H_V = (H_E + 255) / 256;
+    using T = HaloTile<KR, KW, SQ, DIL, 32>;
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, HC = T::HC, PP = T::PP, PQ = T::PQ, PSZ = T::PSZ;
+    constexpr int PLANE = PSZ + T::HSZ, BUF = 3 * PLANE;
+    constexpr int P_V = T::P_V, H_V = T::H_V;
     constexpr int OOR = (int)0x80000000;
     static_assert(PLANE % 4 == 0, "8-byte aligned planes for the transposed reads");
     static_assert(2 * BUF * 2 <= 160 * 1024, "LDS");
@@ -1537,26 +1434,22 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
     const int ke = min(a.nchunks, kb + a.chunks_per_split);
     auto load = [&](int kc, float4 (&rp)[P_V], float4 (&rh)[H_V]) {
         const bool live = kc < ke;
-        const int kcc = live ? kc : kb;
-        const int b = kcc / (d.Hq * cpr);
-        const int rem = kcc - b * d.Hq * cpr;
-        const int i = rem / cpr;
-        const int j0 = (rem - i * cpr) * 32;
-        const long long q0 = (long long)kcc * 32;
+        const HaloChunk ch = halo_chunk(d, cpr, live ? kc : kb);
 #pragma unroll
         for (int q = 0; q < P_V; ++q) {
-            const int off = (live && pc_ok) ? (int)(((q0 + prow0 + 16 * q) * d.ldp + m0 + pc) * 4) : OOR;
+            const int off = (live && pc_ok) ? (int)(((ch.q0 + prow0 + 16 * q) * d.ldp + m0 + pc) * 4) : OOR;
             rp[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rp_, off, 0, 0));
         }
 #pragma unroll
         for (int q = 0; q < H_V; ++q) {
+            // halo_elem's decode inline: calling it here changes every instantiation's register allocation
             const int e = tid + 256 * q;
             const int pix = e / (BN / 4), c = (e % (BN / 4)) * 4;
             const int hr = pix / HC, hc = pix - (pix / HC) * HC;
-            const int ih = i * SQ + dh0 + DIL * hr, iw = j0 * SQ + dwg + hc;
-            const bool ok = live && e < H_E && (unsigned)ih < (unsigned)d.Hqq && (unsigned)iw < (unsigned)d.Wqq &&
+            const int ih = ch.i * SQ + dh0 + DIL * hr, iw = ch.j0 * SQ + dwg + hc;
+            const bool ok = live && e < T::H_E && (unsigned)ih < (unsigned)d.Hqq && (unsigned)iw < (unsigned)d.Wqq &&
                             n0 + c < d.N;
-            const int off = ok ? (int)(((((long long)b * d.Hqq + ih) * d.Wqq + iw) * d.ldq + n0 + c) * 4) : OOR;
+            const int off = ok ? (int)(((((long long)ch.b * d.Hqq + ih) * d.Wqq + iw) * d.ldq + n0 + c) * 4) : OOR;
             rh[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rq_, off, 0, 0));
         }
     };
@@ -1572,13 +1465,12 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
 #pragma unroll
         for (int q = 0; q < H_V; ++q) {
             const int e = tid + 256 * q;
-            if (e < H_E) bf6_put3<PLANE>(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
+            if (e < T::H_E) bf6_put3<PLANE>(B0, PSZ + (e / (BN / 4)) * PQ + (e % (BN / 4)) * 4, rh[q]);
         }
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int lh = lane >> 5, lg = (lane >> 4) & 1, lq = (lane >> 2) & 3, lp = lane & 3;
-    const int tr_row = 8 * lh + lq, tr_col = 16 * lg + 4 * lp;
+    const TrLane tl = tr_lane(lane);
     floatx16 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -1601,11 +1493,11 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
             bf16x8_t af[3];
 #pragma unroll
             for (int pl3 = 0; pl3 < 3; ++pl3)
-                af[pl3] = tr_frag(Ps + pl3 * PLANE + (16 * s + tr_row) * PP + wm * 32 + tr_col, PP);
+                af[pl3] = tr_frag(Ps + pl3 * PLANE + (16 * s + tl.row) * PP + wm * 32 + tl.col, PP);
             static_for<NT>([&](auto J) {
                 constexpr int t = decltype(J)::value;
                 constexpr int hr = t / KW, hc = t % KW;
-                const int ob = (hr * HC + DIL * hc + SQ * (16 * s + tr_row)) * PQ + wn * 32 + tr_col;
+                const int ob = (hr * HC + DIL * hc + SQ * (16 * s + tl.row)) * PQ + wn * 32 + tl.col;
                 bf16x8_t bf[3];
 #pragma unroll
                 for (int pl3 = 0; pl3 < 3; ++pl3) bf[pl3] = tr_frag(Hs + pl3 * PLANE + ob, SQ * PQ);
@@ -1619,32 +1511,9 @@ __global__ __launch_bounds__(256, MINB) void wgrad_halo_bf6_pf2_kernel(const Wgr
         body(kc, 0, pA, hA, pB, hB);
         if (kc + 1 < ke) body(kc + 1, 1, pB, hB, pA, hA);
     }
-    if (do_bias) {  // block-uniform
-        float4* red = reinterpret_cast<float4*>(smem);  // the loop ended with a barrier
-        red[tid] = bsum;
-        __syncthreads();
-        if (tid < BM / 4) {
-            float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int r = 0; r < 256 / (BM / 4); ++r) {
-                const float4 v = red[tid + r * (BM / 4)];
-                s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w;
-            }
-            float* dst = a.bias_slab + (long long)split * d.M + m0 + 4 * tid;
-            const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
-            for (int c = 0; c < 4; ++c)
-                if (m0 + 4 * tid + c < d.M) dst[c] = sv[c];
-        }
-    }
-    const int lr = lane & 31;
-    const long long MN = (long long)d.M * d.N;
-    static_for<NT>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const int n = n0 + wn * 32 + lr;
-        if (n < d.N) {
-            float* out = a.slab + ((long long)split * d.ntaps + t0 + j) * MN + n;
-            slab_store_acc(acc[j], out, m0 + wm * 32, lh, d.M, d.N);
-        }
-    });
+    // block-uniform; no barrier after it: nothing writes the LDS again
+    if (do_bias) bias_block_reduce<BM, 256>(reinterpret_cast<float4*>(smem), bsum, a.bias_slab, split, m0, d.M);
+    slab_store_taps<NT>(acc, a, split, t0, m0 + wm * 32, n0 + wn * 32 + (lane & 31), tl.lh);
 }
 
 // ------------------------------------------------------------------------------------------------
