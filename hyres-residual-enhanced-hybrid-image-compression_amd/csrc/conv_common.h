@@ -1,5 +1,5 @@
-// Internal declarations shared by the convolution (conv.hip, conv_stream.hip through stream_common.h, ru_fused.hip
-// through halo_common.h) and weight-gradient (wgrad.hip) units.
+// Internal declarations shared by the convolution (conv.hip, conv_gemm.hip through conv_epilogue.h, conv_stream.hip
+// through stream_common.h, ru_fused.hip through halo_common.h) and weight-gradient (wgrad.hip) units.
 #pragma once
 #include "common.h"
 
@@ -77,17 +77,26 @@ __device__ __forceinline__ floatx16 bf6_mfma(const bf16x8_t (&a)[3], const bf16x
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
 
-// bf16x6 staging: four fp32 channels split into their three bf16 pieces, one piece per plane (PLANE apart)
-template <int PLANE>
-__device__ __forceinline__ void bf6_put3(__bf16* base, int o, const float4& v) {
+// bf16x6 staging: four fp32 channels split into their three bf16 pieces, one piece per plane (`plane` apart)
+__device__ __forceinline__ void bf6_put3(__bf16* base, int plane, int o, const float4& v) {
     bf16x4_t h, m, l;
     bf6_split4(v, h, m, l);
     *reinterpret_cast<bf16x4_t*>(&base[o]) = h;
-    *reinterpret_cast<bf16x4_t*>(&base[PLANE + o]) = m;
-    *reinterpret_cast<bf16x4_t*>(&base[2 * PLANE + o]) = l;
+    *reinterpret_cast<bf16x4_t*>(&base[plane + o]) = m;
+    *reinterpret_cast<bf16x4_t*>(&base[2 * plane + o]) = l;
+}
+template <int PLANE>
+__device__ __forceinline__ void bf6_put3(__bf16* base, int o, const float4& v) { bf6_put3(base, PLANE, o, v); }
+
+// XCD-aware block order: hardware block hw runs on XCD hw % 8, so XCD x gets the contiguous logical range
+// [x*q + min(x, r), ...) of the nb = 8q + r blocks (a bijection for any nb)
+__device__ __forceinline__ int xcd_logical_block() {
+    const int nb = gridDim.x, hw = blockIdx.x;
+    const int q = nb >> 3, r = nb & 7, x = hw & 7;
+    return x * q + min(x, r) + (hw >> 3);
 }
 
-// ---- the forward convolution kernels' argument block (conv.hip, conv_stream.hip)
+// ---- the forward convolution kernels' argument block (conv.hip, conv_gemm.hip, conv_stream.hip)
 struct ConvArgs {
     hyres_conv_geom g;
     const float* x;
@@ -137,5 +146,11 @@ int launch_stream(const ConvArgs& a, int cfg, hipStream_t st);
 int launch_stream_h(const ConvArgs& a, int cfg, hipStream_t st);
 int launch_stream_hf(const ConvArgs& a, int cfg, hipStream_t st);
 int launch_stream_b6(const ConvArgs& a, int cfg, hipStream_t st);
+
+// ---- the implicit-GEMM family (conv_gemm.hip) as route() and hyres_conv_forward (conv.hip) see it: the kernel of
+// the tiles — fp16 X / Y, f16 operands, bf16x6 (double-buffered or not), fp32 MFMA / scalar loads — and the launch of
+// tile `tile` (the index of TILE_BM / TILE_BN) in load mode `mode` on it, with the split-K reduce when a.nsplit > 1
+enum class ConvGemm { H, F16, B6DB, B6, F32 };
+int launch_tiles(const ConvArgs& a, int tile, int mode, ConvGemm gemm, hipStream_t st);
 
 }  // namespace hyres

@@ -10,7 +10,7 @@ namespace hyres {
 // ------------------------------------------------------------------------------------------------
 // Streaming 1x1 conv (K = Ci <= 128, Co = 32*NT): the K-short pointwise layers of the ResidualUnits /
 // RBBs at 64^2..256^2 sit at the fp32 ridge (64-128 FLOP per output element against 8-12 bytes), and the
-// tiled kernel (conv.hip) runs them as lock-stepped blocks (load, then MFMA, then epilogue), so their MFMA and
+// tiled kernel (conv_gemm.hip) runs them as lock-stepped blocks (load, then MFMA, then epilogue), so their MFMA and
 // HBM phases add instead of overlapping. Here each WAVE streams its own 32-pixel tiles with no block
 // barrier after the one-time weight staging:
 //   * W [Co][K] sits in LDS for the whole (persistent) block, pitch K+4 (conflict-free ds_read_b128);

@@ -18,13 +18,7 @@ constexpr int halo_npx(int D) { return (HALO_R + 2 * D) * halo_hw(D); }  // halo
 constexpr int halo_elems(int D, int V4) { return halo_npx(D) * V4; }
 constexpr int halo_per_thread(int D, int V4, int NT) { return (halo_elems(D, V4) + NT - 1) / NT; }
 
-// XCD-aware block order: hardware block hw runs on XCD hw % 8, so XCD x gets the contiguous logical range
-// [x*q + min(x, r), ...) of the nb = 8q + r blocks (a bijection for any nb)
-__device__ __forceinline__ int xcd_logical_block() {
-    const int nb = gridDim.x, hw = blockIdx.x;
-    const int q = nb >> 3, r = nb & 7, x = hw & 7;
-    return x * q + min(x, r) + (hw >> 3);
-}
+// xcd_logical_block (the XCD-aware block order): conv_common.h
 
 // ---- tile walk of the persistent kernels: block bg of the nb blocks that share the ntiles tiles (one output-channel
 // group). The blocks of one XCD (bg % 8) take one contiguous range of tiles, interleaved, so that vertically adjacent

@@ -1,5 +1,5 @@
 // VGG16 perceptual-loss pieces (src/losses/vgg16.py: VGGLoss, used by src/losses/rd_loss.py:40 when
-// alpha > 0) on gfx950.  The 13 convolutions run on the implicit-GEMM conv kernels (conv.hip); this file
+// alpha > 0) on gfx950.  The 13 convolutions run on the conv kernels (conv.hip, conv_gemm.hip); this file
 // has the rest of the feature pipeline, NHWC:
 //   * torchvision Normalize(mean, std): y = (x - mean_c) / std_c (+ backward g / std_c);
 //   * ReLU forward at a slice boundary (a slice ends on a conv's pre-activation, vgg16.py:29-33);

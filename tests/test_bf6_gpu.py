@@ -1,9 +1,9 @@
-"""fp32 GEMM on the bf16 MFMA ("bf16x6", hyres_conv_tuning key HYRES_TUNE_F32_GEMM = 7, csrc/conv.hip
-conv3x3_wres_bf6_kernel): each fp32 operand is split into three bf16 pieces and each product formed from the six
+"""fp32 GEMM on the bf16 MFMA ("bf16x6", hyres_conv_tuning key HYRES_TUNE_F32_GEMM = 7; bf6_mfma in
+csrc/conv_common.h, csrc/conv.hip conv3x3_wres_bf6_kernel): each fp32 operand is split into three bf16 pieces and each product formed from the six
 cross products with i + j <= 2, fp32 accumulation. Claim under test: it is as accurate as the native fp32 MFMA
 (v_mfma_f32_32x32x2_f32, an fmaf chain) — per product ~2^-25 relative against fp32's 2^-24 rounding — so the fp32
 parity bars of the model hold unchanged. Checked against float64 on the 3x3 64->64 convs the kernel serves
-(forward with bias / residual / ReLU) and on every implicit-GEMM tile family. bf16x6 is the default fp32 GEMM; the
+(forward with bias / residual / ReLU) and on every implicit-GEMM tile family (csrc/conv_gemm.hip). bf16x6 is the default fp32 GEMM; the
 fp32 parity suite (tests/test_parity_gpu.py: conv / deconv / GDN forward and backward, the masked conv, the model train
 step against the reference fixture and the C2-size train step against the fp64 oracle) runs on both GEMMs through its
 ``fp32_gemm`` fixture."""

@@ -1,4 +1,5 @@
-"""Per-kernel fp64 parity of the implicit-GEMM and narrow convolution kernels (csrc/conv.hip) at ragged shapes.
+"""Per-kernel fp64 parity of the implicit-GEMM (csrc/conv_gemm.hip) and narrow (csrc/conv.hip) convolution kernels at
+ragged shapes.
 
 Every case builds a hyres_conv_geom with the hyres_geom_* helpers (hyres_geom_filter_taps for the checkerboard conv),
 re-lays the PyTorch-layout weight on the device with hyres_conv_weight_prep (checked bit for bit against
@@ -45,8 +46,11 @@ split reduces are part of the tiles launch that names them); y from the device G
 every bar is 1e-5: the K depth is at most 5760 products (640 x 3 x 3) of O(1) terms, accumulated in fp32 from products
 that are exact (fp16), fp32-rounded, or bf16x6 (2^-25).  No kernel bug was found.
 
-Mutations (each a scratch copy of csrc/conv.hip with one line changed, values or in-bounds reads only, linked with the
-other objects and run over CASES; failing tests of 1693):
+Mutations (each a scratch copy of the source with one line changed, values or in-bounds reads only, linked with the
+other objects and run over CASES; failing tests of 1693). They were made when the whole family was in csrc/conv.hip;
+epi_store (1-3) is now in csrc/conv_epilogue.h, conv_fwd_body and the split reduces (4-7) in csrc/conv_gemm.hip.
+Mutations 1, 4 and 7 were applied again to that text (shared row stores, one lambda per MFMA flavour): 570, 500 and 1330
+failing, the counts below:
 1. epi_store subtracts the bias: 570, every scalar-epilogue case with a bias (Co = 42 / 70, odd pitches, pointers one
    element off, every narrow case, the scalar split reduce); no float4 case.
 2. epi_store ignores accumulate (fp32 Y): 258, the accumulate cases on the scalar path (epi/*-a*/co42 | ld | ptr,

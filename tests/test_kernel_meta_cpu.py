@@ -155,3 +155,17 @@ def test_stream_kernels_instantiations_and_lds(meta):
     got = {n.replace("hyres::", "").replace("void ", "").split("(")[0]: k["lds"] for k, n in zip(ks, names)}
     assert len(got) == len(ks)
     assert got == want, {n: (want.get(n), got.get(n)) for n in set(want) | set(got) if want.get(n) != got.get(n)}
+
+
+def test_gemm_kernels_instantiations_and_lds(meta):
+    """The implicit-GEMM family (csrc/conv_gemm.hip: conv_fwd_*_kernel and the split-K reduce kernels, epilogue in
+    csrc/conv_epilogue.h) and the narrow kernels that share that epilogue (csrc/conv.hip): the set of instantiations
+    and each one's LDS bytes are those of the build before the family got its file and conv_fwd_body its stages
+    (tests/golden/gemm_kernels.json, written from that build: independent of register allocation)."""
+    with open(os.path.join(HERE, "golden", "gemm_kernels.json")) as f:
+        want = json.load(f)
+    ks = [k for frag in ("conv_fwd_", "conv_splitk_reduce", "conv_narrow") for k in _find(meta, frag)]
+    names = kernel_meta.demangle([k["name"] for k in ks])
+    got = {n.replace("hyres::", "").replace("void ", "").split("(")[0]: k["lds"] for k, n in zip(ks, names)}
+    assert len(got) == len(ks)
+    assert got == want, {n: (want.get(n), got.get(n)) for n in set(want) | set(got) if want.get(n) != got.get(n)}
