@@ -4,6 +4,7 @@
 // eligibility rules and launchers. route() and hyres_conv_forward (conv.hip) reach them through the declarations in
 // conv_common.h; what the four kernels have in common is in stream_common.h.
 #include "stream_common.h"
+#include "wgrad_common.h"
 
 namespace hyres {
 
@@ -519,6 +520,210 @@ void conv1x1_stream_b6_kernel(const ConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Fused backward of a plain fp32 1x1 layer (bf16x6): the input gradient conv1x1_stream_b6_kernel computes and the weight
+// / bias gradient wgrad1x1_bf6_pf2_kernel computes, in one pass over the output gradient gp [P][KG] (the conv's X, the
+// weight gradient's P), which the two kernels each read from HBM and split into bf16 pieces. A persistent block (one
+// per CU, 4 waves) takes a contiguous range of 32-pixel chunks; per chunk all four waves stage gp and the saved input
+// x [P][CX] as three bf16 planes in LDS (wgrad1x1_bf6_pf2_kernel's transposed-read image, loads two chunks ahead in
+// two register sets, two LDS buffers, one barrier per chunk), then
+//   * waves 0, 1 form gx [32][CX] = gp W against the LDS-resident split weights (conv1x1_stream_b6_kernel's Ws image)
+//     — C^T = W gp^T, the gp fragment of lane (r, h) = row r, channels 16s + 8h .. + 7 of the staged planes, the same
+//     pieces (bf6_split4) in the same K order, so gx is bit-identical to the streaming kernel's — and run its coalesced
+//     epilogue (stream_rows_put / StreamEpi::apply: residual, ReLU mask, accumulate; operands two chunks ahead);
+//   * waves 2, 3 accumulate dW [KG][CX] += gp^T x, KG / 2 rows each (four 32 x 32 accumulators, transposed reads), over
+//     all of the block's chunks.
+// Both halves issue 48 bf16 MFMAs per chunk (64 <-> 128 channels). At the end a block writes its dW partial to slab
+// [block][KG][CX] and its column sums of the unsplit gp to bias_slab [block][KG]: the deterministic wgrad_reduce*
+// kernels finish them (no atomics). LDS: weights 51 / 54 KB + 2 x 48 KB of chunk planes + 9 KB of epilogue scratch =
+// 156.3 / 159.5 KB, one block per CU, one wave per SIMD: the kernel claims the whole register file (v255, a255).
+struct Bwd1x1Args {
+    const float* q;    // the saved input [P][ldq]
+    int ldq;
+    float* slab;       // [blocks][KG][CX]
+    float* bias_slab;  // [blocks][KG] or NULL
+    int cps, nchunks;  // chunks per block, 32-pixel chunks in all
+};
+
+template <int NT, int KS, int F>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
+void conv1x1_bwd_fused_b6_kernel(const ConvArgs a, const Bwd1x1Args b) {
+    constexpr int KG = 16 * KS, KP = KG + 8, CX = 32 * NT, WPL = CX * KP;
+    constexpr bool RES = (F & 1) != 0, MASK = (F & 2) != 0, ACC = (F & 4) != 0;
+    constexpr int PP = KG + 32, PQ = CX + 32;  // bf16 row pitches of the chunk planes
+    constexpr int PSZ = KT * PP, QSZ = KT * PQ, PLANE = PSZ + QSZ, BUF = 3 * PLANE;
+    constexpr int P_V = KT * KG / 4 / 256, Q_V = KT * CX / 4 / 256;
+    constexpr int TH = NT / 2;                // co tiles of gx per gx wave
+    constexpr int TMW = KG / 64, TNW = NT;    // dW tiles per dW wave
+    static_assert(NT % 2 == 0 && KG % 64 == 0 && P_V >= 1 && Q_V >= 1 && PLANE % 8 == 0, "shape");
+    __shared__ __attribute__((aligned(16))) __bf16 Ws[3 * WPL];
+    __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
+    __shared__ __attribute__((aligned(16))) float Es[2 * 32 * STREAM_EP];
+    __shared__ __attribute__((aligned(16))) float bs[CX];
+    static_assert((3 * WPL + 2 * BUF) * 2 + (2 * 32 * STREAM_EP + CX) * 4 <= 160 * 1024, "LDS");
+    static_assert(2 * BUF * 2 >= 256 * 16, "the bias reduce borrows the chunk planes");
+    asm volatile("" ::: "v255", "a255");
+    const hyres_conv_geom& g = a.g;
+    const hyres_epilogue& e = a.e;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kb = (int)blockIdx.x * b.cps;
+    const int ke = min(b.nchunks, kb + b.cps);
+    // the gx waves' lane bookkeeping: chunk kc is "tile" kc, chunks from ke on are out of range
+    const StreamWalk w{lane, wave & 1, lane & 31, lane >> 5, lane >> 3, 4 * (lane & 7), 0, 0, ke, a.M};
+    const int lr = w.lr, lh = w.lh;
+    stream_stage_weights<CX, KG>(a.w2, a.ldw, StreamPutBf6<KP, WPL>{Ws});
+    stream_stage_bias<CX>(bs, e);
+    StreamEpi epi{e.act, 0.f, 0.f, 0.f};
+
+    const long long npix = a.M;
+    const __amdgpu_buffer_rsrc_t rp_ = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rq_ = opnd_rsrc(b.q, npix * b.ldq * 4);
+    const __amdgpu_buffer_rsrc_t r_res = opnd_rsrc(RES ? e.res : nullptr, npix * e.ldres * 4);
+    const __amdgpu_buffer_rsrc_t r_mask = opnd_rsrc(MASK ? e.aux0 : nullptr, npix * e.ld0 * 4);
+    const __amdgpu_buffer_rsrc_t r_old = opnd_rsrc(ACC ? a.y : nullptr, npix * g.ldy * 4);
+    // staging: fixed per-thread channel quads, rows tid / (C / 4) + i * 256 / (C / 4) of the chunk
+    const int pc = (tid % (KG / 4)) * 4, prow0 = tid / (KG / 4);
+    const int qc = (tid % (CX / 4)) * 4, qrow0 = tid / (CX / 4);
+    constexpr int PRS = 256 / (KG / 4), QRS = 256 / (CX / 4);
+    auto load = [&](int kc, float4 (&rp)[P_V], float4 (&rq)[Q_V]) {
+#pragma unroll
+        for (int i = 0; i < P_V; ++i) {
+            const int row = kc * KT + prow0 + i * PRS;
+            rp[i] = bload4(rp_, (kc < ke && row < a.M) ? (row * g.ldx + pc) * 4 : STREAM_OOR);
+        }
+#pragma unroll
+        for (int i = 0; i < Q_V; ++i) {
+            const int row = kc * KT + qrow0 + i * QRS;
+            rq[i] = bload4(rq_, (kc < ke && row < a.M) ? (row * b.ldq + qc) * 4 : STREAM_OOR);
+        }
+    };
+    const bool do_bias = b.bias_slab != nullptr;
+    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto store = [&](int buf, const float4 (&rp)[P_V], const float4 (&rq)[Q_V]) {
+        __bf16* B0 = smem + buf * BUF;
+#pragma unroll
+        for (int i = 0; i < P_V; ++i) {
+            if (do_bias) { bsum.x += rp[i].x; bsum.y += rp[i].y; bsum.z += rp[i].z; bsum.w += rp[i].w; }
+            bf6_put3<PLANE>(B0, (prow0 + i * PRS) * PP + pc, rp[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < Q_V; ++i) bf6_put3<PLANE>(B0, PSZ + (qrow0 + i * QRS) * PQ + qc, rq[i]);
+    };
+    // the gx waves' epilogue operands of a chunk's TH co tiles (row layout), one register set per chunk parity
+    const int t0 = (wave & 1) * TH;
+    float4 eres[2][RES ? TH : 1][4], emask[2][MASK ? TH : 1][4], eold[2][ACC ? TH : 1][4];
+    auto load_epi = [&](int kc, auto SET) {
+        constexpr int set = decltype(SET)::value;
+#pragma unroll
+        for (int tt = 0; tt < TH; ++tt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int col = 32 * (t0 + tt) + w.cc;
+                if constexpr (RES) eres[set][tt][q] = bload4(r_res, w.row_off(kc, q, e.ldres, col, 4));
+                if constexpr (MASK) emask[set][tt][q] = bload4(r_mask, w.row_off(kc, q, e.ld0, col, 4));
+                if constexpr (ACC) eold[set][tt][q] = bload4(r_old, w.row_off(kc, q, g.ldy, col, 4));
+            }
+    };
+    const TrLane tl = tr_lane(lane);
+    floatx16 dacc[TMW][TNW];
+#pragma unroll
+    for (int i = 0; i < TMW; ++i)
+#pragma unroll
+        for (int j = 0; j < TNW; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dacc[i][j][r] = 0.f;
+    const bool gxw = wave < 2;  // wave-uniform
+    float4 pA[P_V], qA[Q_V], pB[P_V], qB[Q_V];
+    load(kb, pA, qA);
+    load(kb + 1, pB, qB);
+    if (gxw) {
+        load_epi(kb, std::integral_constant<int, 0>{});
+        load_epi(kb + 1, std::integral_constant<int, 1>{});
+    }
+    store(0, pA, qA);
+    __syncthreads();
+    float* const es = Es + (wave & 1) * 32 * STREAM_EP;
+    // chunk kc sits in LDS buffer CUR; (pn, qn) hold chunk kc + 1 (in flight), (pl, ql) (stored) receive kc + 2
+    auto body = [&](int kc, auto CUR, float4 (&pl)[P_V], float4 (&ql)[Q_V], const float4 (&pn)[P_V],
+                    const float4 (&qn)[Q_V]) {
+        constexpr int cur = decltype(CUR)::value;
+        load(kc + 2, pl, ql);
+        const __bf16* Ps = smem + cur * BUF;
+        const __bf16* Qs = Ps + PSZ;
+        if (gxw) {
+#pragma unroll
+            for (int tt = 0; tt < TH; ++tt) {
+                const int t = t0 + tt;
+                floatx16 acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const int xo = lr * PP + 16 * s + 8 * lh;
+                    const bf16x8_t xb[3] = {*reinterpret_cast<const bf16x8_t*>(&Ps[xo]),
+                                            *reinterpret_cast<const bf16x8_t*>(&Ps[PLANE + xo]),
+                                            *reinterpret_cast<const bf16x8_t*>(&Ps[2 * PLANE + xo])};
+                    const int o = (32 * t + lr) * KP + 16 * s + 8 * lh;
+                    const bf16x8_t wb[3] = {*reinterpret_cast<const bf16x8_t*>(&Ws[o]),
+                                            *reinterpret_cast<const bf16x8_t*>(&Ws[WPL + o]),
+                                            *reinterpret_cast<const bf16x8_t*>(&Ws[2 * WPL + o])};
+                    acc = bf6_mfma(wb, xb, acc);
+                }
+                stream_rows_put(es, w, acc);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int n = 32 * t + w.cc;
+                    const int p = kc * 32 + w.cr + 8 * q;
+                    StreamOpnd op;
+                    if constexpr (RES) op.res = eres[cur][tt][q];
+                    if constexpr (MASK) op.mask = emask[cur][tt][q];
+                    if constexpr (ACC) op.old = eold[cur][tt][q];
+                    const float4 o = epi.apply<F, false, false>(stream_rows_get(es, w, q), ld4(&bs[n]), n, op, false,
+                                                                 [](float4) {});
+                    if (p < a.M) st4(a.y + (long long)p * g.ldy + n, o);
+                }
+            }
+            load_epi(kc + 2, CUR);
+        } else {
+            const int mw = (wave & 1) * (KG / 2);
+#pragma unroll
+            for (int s = 0; s < KT / 16; ++s) {
+                bf16x8_t af[TMW][3], bf[TNW][3];
+#pragma unroll
+                for (int tm = 0; tm < TMW; ++tm)
+#pragma unroll
+                    for (int pl3 = 0; pl3 < 3; ++pl3)
+                        af[tm][pl3] = tr_frag(Ps + pl3 * PLANE + (16 * s + tl.row) * PP + mw + tm * 32 + tl.col, PP);
+#pragma unroll
+                for (int tn = 0; tn < TNW; ++tn)
+#pragma unroll
+                    for (int pl3 = 0; pl3 < 3; ++pl3)
+                        bf[tn][pl3] = tr_frag(Qs + pl3 * PLANE + (16 * s + tl.row) * PQ + tn * 32 + tl.col, PQ);
+#pragma unroll
+                for (int tm = 0; tm < TMW; ++tm)
+#pragma unroll
+                    for (int tn = 0; tn < TNW; ++tn) dacc[tm][tn] = bf6_mfma(af[tm], bf[tn], dacc[tm][tn]);
+            }
+        }
+        if (kc + 1 < ke) store(cur ^ 1, pn, qn);  // block-uniform
+        __syncthreads();
+    };
+    for (int kc = kb; kc < ke; kc += 2) {
+        body(kc, std::integral_constant<int, 0>{}, pA, qA, pB, qB);
+        if (kc + 1 < ke) body(kc + 1, std::integral_constant<int, 1>{}, pB, qB, pA, qA);
+    }
+    if (do_bias)  // block-uniform; the loop ended with a barrier
+        bias_block_reduce<KG, 256>(reinterpret_cast<float4*>(smem), bsum, b.bias_slab, blockIdx.x, 0, KG);
+    if (!gxw) {
+        float* const out = b.slab + (long long)blockIdx.x * KG * CX;
+        const int mw = (wave & 1) * (KG / 2);
+#pragma unroll
+        for (int tm = 0; tm < TMW; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < TNW; ++tn) slab_store_acc(dacc[tm][tn], out + tn * 32 + lr, mw + tm * 32, lh, KG, CX);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // eligibility
 
 // the streamed epilogue operands as the streaming kernels' F bits: residual, ReLU mask, old y
@@ -601,7 +806,9 @@ bool stream_b6_ce() { return g_tune[11] != 0; }
 int stream_b6_cfg(const hyres_conv_geom* g, const hyres_epilogue* e) {
     if (g_tune[7] != 1 || g_tune[10] == 0) return 0;
     if (e->io_f16 || e->f16_operands || e->square_input) return 0;
-    if (!pointwise_same_size(g) || gemm_rows(g) < 65536) return 0;
+    // (hyres_conv_tuning key 24 bit 1 lifts the pixel floor of the BIAS forms: the small-shape tests of the fused backward)
+    const bool floor_off = (g_tune[24] & 2) != 0 && e->kind == HYRES_EPI_BIAS;
+    if (!pointwise_same_size(g) || (gemm_rows(g) < 65536 && !floor_off)) return 0;
     if (e->kind == HYRES_EPI_SA_BWD) {  // the fusion 1x1's input-gradient (coalesced epilogue only)
         const int F = stream_b6_ce() ? sa_bwd_f(g, e) : 0;
         return F ? pack_cfg(6, 4, F) : 0;
@@ -617,6 +824,45 @@ int stream_b6_cfg(const hyres_conv_geom* g, const hyres_epilogue* e) {
     // and ReLU-mask forms only
     if (g->Ci == 128 && g->Co == 128 && F != 0 && F != 2) return 0;
     return pack_cfg(g->Co / 32, g->Ci / 16, F);
+}
+
+// conv1x1_bwd_fused_b6_kernel eligibility (hyres_conv_tuning key 24 bit 0, default on): the input-gradient conv (g, e) is
+// conv1x1_stream_b6_kernel's with the coalesced epilogue, 128 -> 64 channels (64 -> 128 with bit 2), no activation or the ReLU
+// mask, no out2; the weight gradient d is the plain fp32 1x1 of the same pixels with P = the conv's X (same stride) and
+// Q of the conv's Co channels; every row stride a multiple of 4 and every operand within a buffer resource. Returns
+// pack_cfg(NT, KS, F), or 0: the two kernels.
+int bwd1x1_fused_cfg(const hyres_conv_geom* g, const hyres_epilogue* e, const hyres_wgrad_desc* d) {
+    if ((g_tune[24] & 1) == 0 || !stream_b6_ce() || e->kind != HYRES_EPI_BIAS) return 0;
+    const int cfg = stream_b6_cfg(g, e);
+    if (!cfg || e->out2 || (e->act != HYRES_ACT_NONE && e->act != HYRES_ACT_RELU_MASK)) return 0;
+    // 128 -> 64 (the bottleneck tail's backward: gp is the wide operand). 64 -> 128 shares only the 64-channel operand
+    // and measured no faster than its two kernels: built, routed only with key 24 bit 2 (A/B, tests)
+    if (!((g->Ci == 128 && g->Co == 64) || (g->Ci == 64 && g->Co == 128 && (g_tune[24] & 4) != 0))) return 0;
+    if (d->square_q || d->ntaps != 1 || d->dh[0] != 0 || d->dw[0] != 0 || d->sq != 1 || d->Hqq != d->Hq ||
+        d->Wqq != d->Wq || d->f16_operands || d->io_f16)
+        return 0;
+    const long long rows = gemm_rows(g);
+    if (d->M != g->Ci || d->N != g->Co || (long long)d->B * d->Hq * d->Wq != rows || d->ldp != g->ldx) return 0;
+    if (g->ldx % 4 || g->ldy % 4 || d->ldq % 4 || (e->res && e->ldres % 4) || (e->aux0 && e->ld0 % 4)) return 0;
+    const int ld = std::max(std::max(g->ldx, g->ldy), std::max(d->ldq, std::max(e->res ? e->ldres : 0, e->aux0 ? e->ld0 : 0)));
+    if (rows * ld * 4 >= 0x7FFFFFF0LL) return 0;
+    return cfg;
+}
+
+// its plan: one block per CU, each a contiguous range of cps 32-pixel chunks; one slab row per block
+struct Bwd1x1Plan {
+    int nchunks, cps, nsplit, lanes;
+    long long bias_off, total;  // floats: the slab at 0, the [nsplit][M] bias partials
+};
+static Bwd1x1Plan bwd1x1_plan(const hyres_wgrad_desc* d) {
+    Bwd1x1Plan p{};
+    p.nchunks = ceil_div((long long)d->B * d->Hq * d->Wq, KT);
+    p.cps = ceil_div(p.nchunks, std::min(p.nchunks, num_cus()));
+    p.nsplit = ceil_div(p.nchunks, p.cps);
+    p.lanes = wgrad_reduce_lanes((long long)d->M * d->N, p.nsplit);
+    p.bias_off = (long long)p.nsplit * d->M * d->N;
+    p.total = p.bias_off + (long long)p.nsplit * d->M + 4;
+    return p;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -747,4 +993,77 @@ int launch_stream_hf(const ConvArgs& a, int cfg, hipStream_t st) {
     return set_error(HYRES_E_ARG, "conv1x1_stream_hf: no instantiation for NT=%d KC=%d", nt, kc);
 }
 
+template <int NT, int KS>
+static int launch_bwd1x1_f(const ConvArgs& a, const Bwd1x1Args& b, int f, int blocks, hipStream_t st) {
+#define HY_BWD1X1(FV) \
+    case FV: hipLaunchKernelGGL((conv1x1_bwd_fused_b6_kernel<NT, KS, FV>), dim3(blocks), dim3(256), 0, st, a, b); break;
+    switch (f) {
+        HY_BWD1X1(0) HY_BWD1X1(1) HY_BWD1X1(2) HY_BWD1X1(3) HY_BWD1X1(4) HY_BWD1X1(5) HY_BWD1X1(6)
+        default: hipLaunchKernelGGL((conv1x1_bwd_fused_b6_kernel<NT, KS, 7>), dim3(blocks), dim3(256), 0, st, a, b);
+    }
+#undef HY_BWD1X1
+    return HY_LAUNCH_CHECK("conv1x1_bwd_fused_b6_kernel");
+}
+
 }  // namespace hyres
+
+using namespace hyres;
+
+extern "C" {
+
+// every pointer may be NULL (then assumed 16-byte aligned: the host-only query)
+int hyres_conv1x1_bwd_fused_ok(const hyres_conv_geom* g, const hyres_epilogue* e, const hyres_wgrad_desc* d,
+                               const void* gp, const void* q, const void* w2, int ldw, const void* gx) {
+    if (!g || !e || !d || !bwd1x1_fused_cfg(g, e, d)) return 0;
+    return aligned16(gp) && aligned16(q) && aligned16(w2) && aligned16(gx) && aligned16(e->res) && aligned16(e->aux0) &&
+           aligned16(e->bias) && ldw % 4 == 0 && ldw >= g->Ci;
+}
+
+long long hyres_conv1x1_bwd_fused_workspace_bytes(const hyres_wgrad_desc* d) {
+    return d ? 4 * bwd1x1_plan(d).total : 0;
+}
+
+int hyres_conv1x1_bwd_fused_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, const hyres_wgrad_desc* d,
+                                        char* buf, int n) {
+    HY_REQUIRE(g && e && d && buf && n > 0, HYRES_E_ARG, "conv1x1_bwd_fused_kernel_name: bad args");
+    const int cfg = bwd1x1_fused_cfg(g, e, d);
+    HY_REQUIRE(cfg, HYRES_E_SHAPE, "conv1x1_bwd_fused: not eligible");
+    snprintf(buf, n, "conv1x1_bwd_fused_b6_kernel<%d, %d, %d>", cfg_nt(cfg), cfg_k(cfg), cfg_f(cfg));
+    return 0;
+}
+
+int hyres_conv1x1_bwd_fused(const hyres_conv_geom* g, const float* gp, const float* w2, int ldw, float* gx,
+                            const hyres_epilogue* e, const hyres_wgrad_desc* d, const float* q, float* dw, float* dbias,
+                            void* ws, long long ws_bytes, hyres_wgrad_job* jobs, int* njobs, hyres_stream_t s) {
+    HY_REQUIRE(g && gp && w2 && gx && e && d && q && dw && jobs && njobs, HYRES_E_ARG, "conv1x1_bwd_fused: NULL argument");
+    *njobs = 0;
+    HY_REQUIRE(hyres_conv1x1_bwd_fused_ok(g, e, d, gp, q, w2, ldw, gx), HYRES_E_SHAPE,
+               "conv1x1_bwd_fused: not eligible (shape, epilogue, stride or alignment)");
+    const int cfg = bwd1x1_fused_cfg(g, e, d);
+    const Bwd1x1Plan p = bwd1x1_plan(d);
+    HY_REQUIRE(ws && aligned16(ws) && ws_bytes >= 4 * p.total, HYRES_E_WORKSPACE,
+               "conv1x1_bwd_fused: workspace %lld < %lld", ws_bytes, 4 * p.total);
+    ConvArgs a{};
+    a.g = *g; a.x = gp; a.w2 = w2; a.ldw = ldw; a.y = gx; a.e = *e;
+    a.M = g->B * g->Hq * g->Wq;
+    a.nsplit = 1;
+    a.vec4 = 1;
+    a.rsrc_ok = 1;
+    a.x_bytes = (int)((long long)a.M * g->ldx * 4);
+    a.w_bytes = (int)((long long)g->Co * ldw * 4);
+    float* const wsf = (float*)ws;
+    Bwd1x1Args b{q, d->ldq, wsf, dbias ? wsf + p.bias_off : nullptr, p.cps, p.nchunks};
+    hipStream_t st = as_stream(s);
+    const int nt = cfg_nt(cfg), f = cfg_f(cfg);
+    const int rc = nt == 2 ? launch_bwd1x1_f<2, 8>(a, b, f, p.nsplit, st) : launch_bwd1x1_f<4, 4>(a, b, f, p.nsplit, st);
+    if (rc) return rc;
+    jobs[0] = hyres_wgrad_job{wsf, dw, p.nsplit, 1, d->M, d->N, d->sm, d->sn, d->st, d->accumulate, p.lanes, 0};
+    *njobs = 1;
+    if (dbias) {
+        jobs[1] = hyres_wgrad_job{wsf + p.bias_off, dbias, p.nsplit, 1, d->M, 1, 1, 0, 0, d->accumulate, p.lanes, 0};
+        *njobs = 2;
+    }
+    return 0;
+}
+
+}  // extern "C"

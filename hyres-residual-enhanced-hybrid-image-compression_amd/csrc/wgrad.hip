@@ -1828,6 +1828,7 @@ static int reduce_lx(long long total, int nsplit) {
     if ((total + 31) / 32 >= 1024) return 8;
     return 4;
 }
+int wgrad_reduce_lanes(long long total, int nsplit) { return reduce_lx(total, nsplit); }
 
 // Column sums of a [P][C] (pixel stride ld) matrix, deterministic two-pass.
 // Pass 1: a block owns a row range; its 256 threads are laid out TR x TC over (rows, channel groups of

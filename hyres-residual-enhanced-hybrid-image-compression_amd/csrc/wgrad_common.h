@@ -20,6 +20,9 @@ struct WgradArgs {
     float* bias_slab;  // [nsplit][M] column sums of P (the bias gradient) or NULL
 };
 
+// lanes per block row of the split reduce (wgrad.hip) for `total` outputs in nsplit partials
+int wgrad_reduce_lanes(long long total, int nsplit);
+
 template <typename F, int... Is>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
     (f(std::integral_constant<int, Is>{}), ...);

@@ -113,6 +113,14 @@ _SIGS = {
     "hyres_conv_wgrad_deferred": (_I, [ctypes.POINTER(WgradDesc), _P, _P, _P, _P, _P, _LL, ctypes.POINTER(WgradJob),
                                        ctypes.POINTER(ctypes.c_int), _P]),
     "hyres_wgrad_reduce_jobs": (_I, [ctypes.POINTER(WgradJob), _I, _P]),
+    "hyres_conv1x1_bwd_fused_ok": (_I, [ctypes.POINTER(ConvGeom), ctypes.POINTER(Epilogue), ctypes.POINTER(WgradDesc),
+                                        _P, _P, _P, _I, _P]),
+    "hyres_conv1x1_bwd_fused_workspace_bytes": (_LL, [ctypes.POINTER(WgradDesc)]),
+    "hyres_conv1x1_bwd_fused_kernel_name": (_I, [ctypes.POINTER(ConvGeom), ctypes.POINTER(Epilogue),
+                                                 ctypes.POINTER(WgradDesc), ctypes.c_char_p, _I]),
+    "hyres_conv1x1_bwd_fused": (_I, [ctypes.POINTER(ConvGeom), _P, _P, _I, _P, ctypes.POINTER(Epilogue),
+                                     ctypes.POINTER(WgradDesc), _P, _P, _P, _P, _LL, ctypes.POINTER(WgradJob),
+                                     ctypes.POINTER(ctypes.c_int), _P]),
     "hyres_ru_fused_f16_ok": (_I, [_I, _I, _I, _I]),
     "hyres_ru_fused_f16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "hyres_colsum": (_I, [_P, _I, _I, _I, _P, _I, _P, _LL, _I, _P]),

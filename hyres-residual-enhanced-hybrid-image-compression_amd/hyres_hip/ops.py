@@ -775,8 +775,18 @@ class WgradBatch:
     @classmethod
     def launch(cls, desc: L.WgradDesc, p_ptr: int, q_ptr: int, dst: torch.Tensor, device,
                dbias: Optional[torch.Tensor]) -> None:
-        lib = L.load()
-        nbytes = int(lib.hyres_wgrad_workspace_bytes(ctypes.byref(desc)))
+        nbytes = int(L.load().hyres_wgrad_workspace_bytes(ctypes.byref(desc)))
+
+        def issue(ws, jobs, nj, stream):
+            L.call("hyres_conv_wgrad_deferred", ctypes.byref(desc), p_ptr, q_ptr, dst.data_ptr(),
+                   None if dbias is None else dbias.data_ptr(), ws.data_ptr(), ws.numel(), jobs, nj, stream)
+
+        cls.submit(nbytes, dst, dbias, device, issue)
+
+    @classmethod
+    def submit(cls, nbytes: int, dst: torch.Tensor, dbias: Optional[torch.Tensor], device, issue) -> None:
+        """Run ``issue(ws, jobs, njobs, stream)`` — a launch that leaves its split reduce as up to two jobs writing
+        ``dst`` / ``dbias`` from a slab in ``ws`` (``nbytes``) — and queue those jobs."""
         stream = L.stream()
         ent = cls._entry(int(stream.value or 0))
         outs = [(dst.data_ptr(), dst.data_ptr() + 4 * dst.numel())]
@@ -788,9 +798,7 @@ class WgradBatch:
         ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=device)
         jobs = (L.WgradJob * 2)()
         nj = ctypes.c_int(0)
-        L.call("hyres_conv_wgrad_deferred", ctypes.byref(desc), p_ptr, q_ptr, dst.data_ptr(),
-               None if dbias is None else dbias.data_ptr(), ws.data_ptr(), ws.numel(), jobs, ctypes.byref(nj),
-               stream)
+        issue(ws, jobs, ctypes.byref(nj), stream)
         if nj.value:
             ent["jobs"].extend(jobs[i] for i in range(nj.value))
             ent["keep"].append(ws)
@@ -864,6 +872,56 @@ def _wgrad_launch(desc, p_ptr, q_ptr, dst, device, dbias, slot):
         name = (f"WGRAD B{d.B} P {d.Hq}x{d.Wq}x{d.M} Q {d.Hqq}x{d.Wqq}x{d.N} taps{d.ntaps} sq{d.sq}"
                 f"{' sqr' if d.square_q else ''}")
         KernelTimer.table.append((name, s0, s1, flops, nbytes_alg))
+
+
+def bwd1x1_fused_variant(g: L.ConvGeom, e: L.Epilogue, d: L.WgradDesc) -> str:
+    """The fused 1x1 backward kernel of (g, e, d), named by the launcher's choice function."""
+    buf = ctypes.create_string_buffer(96)
+    L.call("hyres_conv1x1_bwd_fused_kernel_name", ctypes.byref(g), ctypes.byref(e), ctypes.byref(d), buf, len(buf))
+    return buf.value.decode()
+
+
+def _bwd1x1_fused(g: L.ConvGeom, e: L.Epilogue, d: L.WgradDesc, gp_ptr: int, q_ptr: int, w2: torch.Tensor, ldw: int,
+                  y_ptr: int, dst: torch.Tensor, dbias: Optional[torch.Tensor], device) -> bool:
+    """The input gradient (g, e) and the weight / bias gradient d of a plain fp32 1x1 conv in one launch
+    (hyres_conv1x1_bwd_fused) where the library's predicate holds; False: the caller launches the two kernels.
+    The split reduce is deferred (WgradBatch) or run at once, as _wgrad does."""
+    if device.type != "cuda" or SideStream.enabled:
+        return False
+    lib = L.load()
+    if not lib.hyres_conv1x1_bwd_fused_ok(ctypes.byref(g), ctypes.byref(e), ctypes.byref(d), gp_ptr, q_ptr,
+                                          w2.data_ptr(), ldw, y_ptr):
+        return False
+    nbytes = int(lib.hyres_conv1x1_bwd_fused_workspace_bytes(ctypes.byref(d)))
+    db_ptr = None if dbias is None else dbias.data_ptr()
+
+    def issue(ws, jobs, nj, stream):
+        L.call("hyres_conv1x1_bwd_fused", ctypes.byref(g), gp_ptr, w2.data_ptr(), ldw, y_ptr, ctypes.byref(e),
+               ctypes.byref(d), q_ptr, dst.data_ptr(), db_ptr, ws.data_ptr(), ws.numel(), jobs, nj, stream)
+
+    timed = KernelTimer.enabled
+    if timed:
+        s0 = torch.cuda.Event(enable_timing=True)
+        s1 = torch.cuda.Event(enable_timing=True)
+        s0.record()
+    if WgradBatch.enabled and not (timed and KernelTimer.all_convs):
+        WgradBatch.submit(nbytes, dst, dbias, device, issue)
+    else:
+        ws = _ws(nbytes, device, slot=7)
+        jobs = (L.WgradJob * 2)()
+        nj = ctypes.c_int(0)
+        issue(ws, jobs, ctypes.byref(nj), L.stream())
+        L.call("hyres_wgrad_reduce_jobs", jobs, nj.value, L.stream())
+    if timed:
+        s1.record()
+        q = d.B * d.Hq * d.Wq
+        flops = conv_flops(g) + 2.0 * q * d.M * d.N
+        nbytes_alg = conv_bytes(g, e) + 4.0 * q * d.N + 4.0 * d.M * d.N
+        name = bwd1x1_fused_variant(g, e, d)
+        KernelTimer.events.append((s0, s1, flops, nbytes_alg, name))
+        if KernelTimer.all_convs:
+            KernelTimer.table.append((f"BWD1x1 B{g.B} {g.Hi}x{g.Wi}x{g.Ci}->{g.Co} [{name}]", s0, s1, flops, nbytes_alg))
+    return True
 
 
 def _act_backward(y: Node, gy: torch.Tensor, gy_ld: int, act: int, pre: Optional[torch.Tensor],
@@ -962,6 +1020,7 @@ def conv2d(tape: Optional[Tape], x: Node, weight: torch.Tensor, bias: Optional[t
             add2d(gp, gpld, tgt, res.grad_ld(), P, Co, acc)
         if wants_grad(bias) and not wants_grad(weight):
             _colsum_into(gp, P, Co, gpld, param_grad(bias))
+        d = None
         if wants_grad(weight):
             d = L.WgradDesc()
             L.call("hyres_wgrad_desc_conv2d", ctypes.byref(d), B, H, W, Ci, x.ld, Co, gpld, KH, KW, stride,
@@ -971,21 +1030,36 @@ def conv2d(tape: Optional[Tape], x: Node, weight: torch.Tensor, bias: Optional[t
             d.f16_operands = f16 * AMP_WGRAD_F16
             # P = the (fp16 under AMP) gradient, Q = the saved input activation
             d.io_f16 = L.dt_mask(gp, x, 1, 2)
+
+        def wgrad():
             _wgrad(d, gp.data_ptr(), x.ptr(), param_grad(weight), x.device,
                    param_grad(bias) if wants_grad(bias) else None, keep=(gp, x.v), side=True)
-        if x.rg:
-            ed = L.Epilogue()
-            ed.kind = L.EPI_BIAS
-            tgt, acc, _keep = x.grad_target_epi(ed)
-            gd = _filter_taps(_geom("hyres_geom_conv2d_dgrad", B, H, W, Ci, x.grad_ld(), Co, gpld, KH, KW, stride,
-                                    pad, dil), mask)
-            w2d = _prepped(weight, gd, L.WPREP_CONV_DGRAD, Ci_w, Co, KH, KW, pad, mask)
-            ed.accumulate = acc
-            ed.f16_operands = f16
-            ed.io_f16 = _dgrad_io(gp, x)
-            x.relu_mask_epilogue(ed, acc)
-            x.prelu_mask_epilogue(ed, acc, gd)
-            _launch_conv(gd, gp.data_ptr(), w2d, gd.ntaps * Co, tgt.data_ptr(), ed)
+
+        if not x.rg:
+            if d is not None:
+                wgrad()
+            return
+        one = KH == 1 and KW == 1 and stride == 1 and d is not None and mask is None
+        if d is not None and not one:
+            wgrad()
+        ed = L.Epilogue()
+        ed.kind = L.EPI_BIAS
+        tgt, acc, _keep = x.grad_target_epi(ed)
+        gd = _filter_taps(_geom("hyres_geom_conv2d_dgrad", B, H, W, Ci, x.grad_ld(), Co, gpld, KH, KW, stride,
+                                pad, dil), mask)
+        w2d = _prepped(weight, gd, L.WPREP_CONV_DGRAD, Ci_w, Co, KH, KW, pad, mask)
+        ed.accumulate = acc
+        ed.f16_operands = f16
+        ed.io_f16 = _dgrad_io(gp, x)
+        x.relu_mask_epilogue(ed, acc)
+        x.prelu_mask_epilogue(ed, acc, gd)
+        if one:
+            # a plain 1x1: one kernel for both gradients where the library takes it (hyres_conv1x1_bwd_fused_ok)
+            if _bwd1x1_fused(gd, ed, d, gp.data_ptr(), x.ptr(), w2d, gd.ntaps * Co, tgt.data_ptr(), param_grad(weight),
+                             param_grad(bias) if wants_grad(bias) else None, x.device):
+                return
+            wgrad()
+        _launch_conv(gd, gp.data_ptr(), w2d, gd.ntaps * Co, tgt.data_ptr(), ed)
 
     tape.push(bwd)
     return y

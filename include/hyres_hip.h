@@ -234,7 +234,14 @@ int hyres_conv_plan(const hyres_conv_geom* g, const hyres_epilogue* e, int* tile
                                        * gain per launch or in the step (profiles/r6v_wg5.txt, r6v_wg5_step_ab.txt) */
 #define HYRES_TUNE_THIN_WINDOW 23     /* 1 (default): the thin (3-channel) 3x3 weight gradients keep each pixel's 3 x 3 Q window
                                        * in registers, sliding one column per pixel (bit-identical); 0: nine LDS reads per pixel */
-#define HYRES_TUNE_KEYS 24
+#define HYRES_TUNE_BWD1X1_FUSED 24    /* bit 0 (default 1): the backward of the fp32 1x1 layers with a 128-channel output
+                                       * gradient and a 64-channel input on >= 65536 pixels in one kernel
+                                       * (conv1x1_bwd_fused_b6_kernel: input gradient + weight / bias gradient partials from
+                                       * one read of the output gradient); 0: conv1x1_stream_b6_kernel +
+                                       * wgrad1x1_bf6_pf2_kernel (A/B). Bit 1 (default 0, tests): no pixel floor for it and
+                                       * for conv1x1_stream_b6_kernel's BIAS forms. Bit 2 (default 0): also the 64-channel
+                                       * gradient / 128-channel input layers (measured no faster than the two kernels) */
+#define HYRES_TUNE_KEYS 25
 int hyres_conv_tuning(int key, int value, int* old);
 
 /* Weight gradient:  dW[t][m][n] = sum_q P[q][m] * Q[shift_t(q)][n]  over a base grid q (B,Hq,Wq).
@@ -300,6 +307,21 @@ int hyres_conv_wgrad_deferred(const hyres_wgrad_desc* d, const float* p, const f
                               float* dbias, void* workspace, long long ws_bytes, hyres_wgrad_job* jobs,
                               int* njobs, hyres_stream_t s);
 int hyres_wgrad_reduce_jobs(const hyres_wgrad_job* jobs, int n, hyres_stream_t s);
+
+/* Fused backward of a plain fp32 1x1 Conv2d (bf16x6, HYRES_TUNE_BWD1X1_FUSED): the input gradient
+ * hyres_conv_forward(g, gp, w2, ldw, gx, e) computes (bit-identical to conv1x1_stream_b6_kernel's) and the partials of
+ * the weight / bias gradient hyres_conv_wgrad_deferred(d, gp, q, dw, dbias) computes, in one launch that reads the
+ * output gradient gp once. The split reduce comes back as jobs, as from hyres_conv_wgrad_deferred.
+ * hyres_conv1x1_bwd_fused_ok: whether (g, e, d) and the operands' alignment (a NULL pointer: assumed aligned) are
+ * eligible; otherwise the caller launches the two kernels. */
+int hyres_conv1x1_bwd_fused_ok(const hyres_conv_geom* g, const hyres_epilogue* e, const hyres_wgrad_desc* d,
+                               const void* gp, const void* q, const void* w2, int ldw, const void* gx);
+long long hyres_conv1x1_bwd_fused_workspace_bytes(const hyres_wgrad_desc* d);
+int hyres_conv1x1_bwd_fused_kernel_name(const hyres_conv_geom* g, const hyres_epilogue* e, const hyres_wgrad_desc* d,
+                                        char* buf, int n);
+int hyres_conv1x1_bwd_fused(const hyres_conv_geom* g, const float* gp, const float* w2, int ldw, float* gx,
+                            const hyres_epilogue* e, const hyres_wgrad_desc* d, const float* q, float* dw, float* dbias,
+                            void* workspace, long long ws_bytes, hyres_wgrad_job* jobs, int* njobs, hyres_stream_t s);
 
 /* Fused ResidualUnit / ResidualBottleneckBlock forward, autocast inference with fp16 activations (round 4):
  * y = [relu](x + W3 * relu(W2 (*) relu(W1 * x + b1) + b2) + b3) in ONE launch, t1 / t2 kept on chip (fp16, the
