@@ -30,6 +30,16 @@ inline bool aligned_v4(const void* p, bool half) { return half ? aligned8(p) : a
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// The kernels that finish per-block partials, one per summation order (pointwise.hip; DESIGN "Reduction orders"). Each
+// thread of one 256-thread block walks the partials i = tid, tid + 256, ...; block_sum256 folds the 256 sums.
+//   prelu_slope_sum:   dst[0] += sum, one running sum per thread (the conv PReLU-mask epilogues, hyres_se_bwd_prelu)
+//   sum_partials8:     out[0] (+)= sum, eight running sums per thread, eight loads in flight, paired at the end
+//   sum_partials_cols: one block per column k of part[nb][stride]: (k < n0 ? dst0[k] : dst1[k - n0]) += sum_i part[i][k]
+int prelu_slope_sum(const void* partials, int n, const void* dst, hipStream_t st);
+int sum_partials8(const float* part, int n, float* out, int accumulate, hipStream_t st, const char* what);
+int sum_partials_cols(const float* part, int nb, int stride, float* dst0, int n0, float* dst1, int n1, hipStream_t st,
+                      const char* what);
+
 // Operand dtypes of the element-wise and MultiScaleRefine entry points (HYRES_DT_*, hyres_hip.h). The masks that have
 // kernels: fp32, fp16 saved activations, fp16 activations with fp16 gradients. dispatch_hg calls f(H, G) with the two
 // flags as std::bool_constant values, which serve as template arguments inside f.
@@ -40,6 +50,13 @@ inline int dispatch_hg(int dt, F&& f) {
     if (dt & HYRES_DT_GRAD16) return f(std::true_type{}, std::true_type{});
     if (dt & HYRES_DT_ACT16) return f(std::true_type{}, std::false_type{});
     return f(std::false_type{}, std::false_type{});
+}
+
+// f(A, B) with two independent flags as std::bool_constant values: every combination
+template <class F>
+inline int dispatch_bool2(bool a, bool b, F&& f) {
+    if (a) return b ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return b ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
 }
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));

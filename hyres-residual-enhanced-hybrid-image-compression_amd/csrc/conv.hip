@@ -666,20 +666,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wres_bf6_kernel(const ConvArgs
     }
 }
 
-// HYRES_ACT_PRELU_MASK's second kernel: the block partials summed in a fixed order, added to the slope gradient
-__global__ __launch_bounds__(256) void prelu_slope_sum_kernel(const float* part, int n, float* dst) {
-    __shared__ float red[256];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) dst[0] += red[0];
-}
-
 // ------------------------------------------------------------------------------------------------
 // Narrow output (Co <= 4: the 3-channel image-side layers — g_s's last deconv 128->3, MultiScaleRefine's
 // conv 64->3 and the input-gradient of its conv 3->64). A 32-wide MFMA column tile would be >90% padding,
@@ -1344,13 +1330,6 @@ static bool wres32_ok(const hyres_conv_geom* g, const hyres_epilogue* e) {
     // halo radius 1, or 2 for the bf16x6 kernel (dilation-2 3x3s: its D = 2 build)
     if (wres_halo(g) > (wres_bf6() && g_tune[9] != 0 ? 2 : 1)) return false;
     return wres_size_ok(g, g->Co / 32);
-}
-
-// the PReLU-mask epilogues leave one slope-gradient partial per block: summed in a fixed order and added to dst
-int hyres::prelu_slope_sum(const void* partials, int n, const void* dst, hipStream_t st) {
-    hipLaunchKernelGGL(prelu_slope_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, n,
-                       (float*)const_cast<void*>(dst));
-    return HY_LAUNCH_CHECK("prelu_slope_sum_kernel");
 }
 
 static int launch_wres16(const ConvArgs& a, hipStream_t st) {

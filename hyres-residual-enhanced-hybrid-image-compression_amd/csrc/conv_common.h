@@ -132,9 +132,6 @@ inline bool pointwise_same_size(const hyres_conv_geom* g) {
            g->Hi == g->Hq && g->Wi == g->Wq && g->Ho == g->Hq && g->Wo == g->Wq;
 }
 
-// the PReLU-mask epilogues leave one slope-gradient partial per block: summed in a fixed order and added to dst (conv.hip)
-int prelu_slope_sum(const void* partials, int n, const void* dst, hipStream_t st);
-
 // ---- the streaming 1x1 family (conv_stream.hip) as route() and hyres_conv_forward (conv.hip) see it: eligibility
 // (pack_cfg(NT, KC or KS, F), or 0) and launch of the instantiation a cfg names
 int stream_cfg(const hyres_conv_geom* g, const hyres_epilogue* e);

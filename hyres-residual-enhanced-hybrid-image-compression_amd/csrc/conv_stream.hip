@@ -362,7 +362,7 @@ void conv1x1_stream_b6_kernel(const ConvArgs a) {
     // PM (F & 32, round 6, with SAB): HYRES_ACT_PRELU_MASK on output channels [0, 64) — MultiScaleRefine's scale-1
     // block writes PReLU(.) into multi[..., 0:64], so d multi's first 64 channels are that PReLU output's whole
     // gradient: o = pre > 0 ? o : slope * o (pre = aux1 [P][ld1]), sum_{pre <= 0} pre * o into this block's partial
-    // (out2[block]); the slope gradient (res, ADDED) by prelu_slope_sum_kernel after the launch
+    // (out2[block]); the slope gradient (res, ADDED) by prelu_slope_sum() after the launch
     constexpr bool PM = (F & 32) != 0;
     static_assert(!PM || (SAB && !ACC && NT >= 2), "PReLU mask: the SA_BWD form without accumulate");
     constexpr int WPL = CO * KP;  // bf16 per weight plane

@@ -9,7 +9,7 @@
 //   * EntropyBottleneck: per-channel MLP 1-3-3-3-3-1 with softplus weights and tanh gates,
 //     lik = max(sigmoid(L(v+.5)) - sigmoid(L(v-.5)), 1e-9)
 // Layout: all activations NHWC; y/scales/means are [B,H,W,C] with C = M (192).
-#include "common.h"
+#include "reduce_common.h"
 
 namespace hyres {
 
@@ -294,13 +294,8 @@ __global__ __launch_bounds__(256) void eb_bwd_kernel(const float* z_q, const flo
     __shared__ float red[256];
     float* out = gws + ((long long)blockIdx.y * C + c) * HYRES_EB_REC;
     for (int k = 0; k < EB_NP; ++k) {
-        red[threadIdx.x] = gp[k];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[k] = red[0];
+        const float r = block_sum256(gp[k], red);
+        if (threadIdx.x == 0) out[k] = r;
         __syncthreads();
     }
 }

@@ -1,6 +1,6 @@
 // Elementwise, reduction and optimiser kernels of the HyRES hot path (gfx950).
 // All are HBM-bound streams: grid-stride loops, 256-thread blocks, float4 where the layout allows.
-#include "common.h"
+#include "reduce_common.h"
 
 #include <mutex>
 
@@ -18,16 +18,6 @@ int set_error(int code, const char* fmt, ...) {
     return code;
 }
 int ok() { return HYRES_OK; }
-
-static inline int grid_for(long long n, int per_thread = 1) {
-    long long b = (n / per_thread + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 8192) b = 8192;
-    return (int)b;
-}
-
-#define GRID_STRIDE(i, n) \
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
 
 // ---------------------------------------------------------------- layout
 __global__ void nchw_to_nhwc_kernel(const float* x, float* y, int B, int C, int H, int W, int ldy) {
@@ -92,18 +82,33 @@ __global__ void prelu_bwd_kernel(const float* x, int ldx, const float* g, int ld
         int c = (int)(i - p * C);
         float xv = ldv<H>(x, p * ldx + c);
         float gv = ldv<G>(g, p * ldg + c);
-        stv<G>(gx, p * ldgx + c, xv > 0.f ? gv : a * gv);
-        if (!(xv > 0.f)) s += xv * gv;
+        stv<G>(gx, p * ldgx + c, prelu_bwd_elem(xv, gv, a, s));
     }
-    // block reduce
     __shared__ float red[256];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
+    const float r = block_sum256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+// ---- the kernels that finish per-block partials, one per summation order (launchers declared in common.h)
+// one running sum per thread: dst[0] += sum
+__global__ __launch_bounds__(256) void sum_partials_serial_kernel(const float* part, int n, float* dst) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+    const float r = block_sum256(s, red);
+    if (threadIdx.x == 0) dst[0] += r;
+}
+// one block per column k of part[nb][stride], ADDED to dst0[k] (k < n0) or dst1[k - n0]
+__global__ __launch_bounds__(256) void sum_partials_cols_kernel(const float* part, int nb, int stride, float* dst0, int n0,
+                                                                float* dst1) {
+    __shared__ float red[256];
+    const int k = blockIdx.x;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nb; i += 256) s += part[(long long)i * stride + k];
+    const float r = block_sum256(s, red);
+    if (threadIdx.x == 0) {
+        if (k < n0) dst0[k] += r;
+        else dst1[k - n0] += r;
     }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 __global__ void sum_partials_kernel(const float* part, int nb, float* out, int accumulate) {
     __shared__ float red[256];
@@ -116,14 +121,8 @@ __global__ void sum_partials_kernel(const float* part, int nb, float* out, int a
 #pragma unroll
     for (int k = 0; k < 8; ++k)
         if (i + k * 256 < nb) s8[k] += part[i + k * 256];
-    const float s = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + red[0] : red[0];
+    const float r = block_sum256(((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7])), red);
+    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + r : r;
 }
 __global__ void attn_gate_fwd_kernel(const float* a, const float* b, const float* x, float* out, long long n) {
     GRID_STRIDE(i, n) {
@@ -255,22 +254,16 @@ __global__ __launch_bounds__(256) void prelu_bwd4_kernel(const float* x, int ldx
         const int p = i / C4, c = 4 * (i - (i / C4) * C4);
         const float4 xv = ldv4<H>(x, (long long)p * ldx + c);
         const float4 gv = ldv4<G>(g, (long long)p * ldg + c);
-        stv4<G>(gx, (long long)p * ldgx + c,
-                make_float4(xv.x > 0.f ? gv.x : a * gv.x, xv.y > 0.f ? gv.y : a * gv.y, xv.z > 0.f ? gv.z : a * gv.z,
-                            xv.w > 0.f ? gv.w : a * gv.w));
-        if (!(xv.x > 0.f)) s += xv.x * gv.x;
-        if (!(xv.y > 0.f)) s += xv.y * gv.y;
-        if (!(xv.z > 0.f)) s += xv.z * gv.z;
-        if (!(xv.w > 0.f)) s += xv.w * gv.w;
+        float4 o;  // x, y, z, w: the element order of every PReLU fold's slope sum
+        o.x = prelu_bwd_elem(xv.x, gv.x, a, s);
+        o.y = prelu_bwd_elem(xv.y, gv.y, a, s);
+        o.z = prelu_bwd_elem(xv.z, gv.z, a, s);
+        o.w = prelu_bwd_elem(xv.w, gv.w, a, s);
+        stv4<G>(gx, (long long)p * ldgx + c, o);
     }
     __shared__ float red[256];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    const float r = block_sum256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 static inline bool vec4_2d(long long P, int C, const void* a, int lda, const void* b, int ldb, const void* c, int ldc) {
@@ -354,22 +347,11 @@ __global__ void seed_advance_kernel(unsigned long long* seed_dev) {
 }
 
 // ---------------------------------------------------------------- reductions
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int k = blockDim.x / 2; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    float r = red[0];
-    __syncthreads();
-    return r;
-}
 __global__ void sum_log_kernel(const float* x, long long n, float* part) {
     __shared__ float red[256];
     float s = 0.f;
     GRID_STRIDE(i, n) s += logf(x[i]);
-    float r = block_sum(s, red);
+    const float r = block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 __global__ void sum_sqdiff_kernel(const float* a, const float* b, long long n, float* part) {
@@ -379,7 +361,7 @@ __global__ void sum_sqdiff_kernel(const float* a, const float* b, long long n, f
         float d = a[i] - b[i];
         s += d * d;
     }
-    float r = block_sum(s, red);
+    const float r = block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 // Sum of squares for clip_grad_norm_ and GradScaler's found_inf, accumulated AND returned in fp64: a large
@@ -393,25 +375,15 @@ __global__ void sumsq_kernel(const float* x, long long n, double* part) {
         const double v = (double)x[i];
         s += v * v;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    const double r = block_sum256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 __global__ void sumsq_final_kernel(const double* part, int nb, double* out) {
     __shared__ double red[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
+    const double r = block_sum256(s, red);
+    if (threadIdx.x == 0) out[0] = r;
 }
 __global__ void scale_recip_kernel(const float* x, const float* coef, float scale, float* g, long long n) {
     const float c = coef[0] * scale;
@@ -540,6 +512,21 @@ __global__ void grad_scaler_update_kernel(const double* sumsq, float* scale, flo
 
 using namespace hyres;
 
+int hyres::prelu_slope_sum(const void* partials, int n, const void* dst, hipStream_t st) {
+    hipLaunchKernelGGL(sum_partials_serial_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, n,
+                       (float*)const_cast<void*>(dst));
+    return HY_LAUNCH_CHECK("prelu_slope_sum");
+}
+int hyres::sum_partials8(const float* part, int n, float* out, int accumulate, hipStream_t st, const char* what) {
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, part, n, out, accumulate);
+    return HY_LAUNCH_CHECK(what);
+}
+int hyres::sum_partials_cols(const float* part, int nb, int stride, float* dst0, int n0, float* dst1, int n1,
+                             hipStream_t st, const char* what) {
+    hipLaunchKernelGGL(sum_partials_cols_kernel, dim3(n0 + n1), dim3(256), 0, st, part, nb, stride, dst0, n0, dst1);
+    return HY_LAUNCH_CHECK(what);
+}
+
 extern "C" {
 
 int hyres_version(void) { return 10000; }
@@ -618,8 +605,7 @@ static int prelu_bwd_impl(const float* x, int ldx, const float* g, int ldg, floa
                            C, slope, (float*)ws);
     int rc = HY_LAUNCH_CHECK("prelu_bwd");
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, as_stream(s), (const float*)ws, nb, dslope, 1);
-    return HY_LAUNCH_CHECK("prelu_bwd_final");
+    return sum_partials8((const float*)ws, nb, dslope, 1, as_stream(s), "prelu_bwd_final");
 }
 }  // extern "C++"
 int hyres_prelu_bwd(const void* x, int ldx, const void* g, int ldg, void* gx, int ldgx, long long P, int C,
@@ -802,8 +788,7 @@ static int reduce2(void (*k)(const float*, long long, float*), const float* x, l
     hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, as_stream(s), x, n, (float*)ws);
     int rc = HY_LAUNCH_CHECK(name);
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, as_stream(s), (const float*)ws, nb, out, 0);
-    return HY_LAUNCH_CHECK(name);
+    return sum_partials8((const float*)ws, nb, out, 0, as_stream(s), name);
 }
 int hyres_sum_log(const float* x, long long n, float* out, void* ws, long long ws_bytes, hyres_stream_t s) {
     HY_REQUIRE(x && out, HYRES_E_ARG, "sum_log: NULL");
@@ -827,8 +812,7 @@ int hyres_sum_sqdiff(const float* a, const float* b, long long n, float* out, vo
     hipLaunchKernelGGL(sum_sqdiff_kernel, dim3(nb), dim3(256), 0, as_stream(s), a, b, n, (float*)ws);
     int rc = HY_LAUNCH_CHECK("sum_sqdiff");
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, as_stream(s), (const float*)ws, nb, out, 0);
-    return HY_LAUNCH_CHECK("sum_sqdiff_final");
+    return sum_partials8((const float*)ws, nb, out, 0, as_stream(s), "sum_sqdiff_final");
 }
 int hyres_scale_recip(const float* x, const float* coef, float scale, float* g, long long n, hyres_stream_t s) {
     HY_REQUIRE(x && coef && g, HYRES_E_ARG, "scale_recip: NULL");

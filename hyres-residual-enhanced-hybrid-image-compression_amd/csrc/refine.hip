@@ -1,26 +1,12 @@
 // MultiScaleRefine pieces (models/layers/enhancement.py) on gfx950: bilinear resampling with
 // PyTorch's align_corners=False source-index rule, SEBlock, SpatialAttention (CBAM SA).
 // Activations are NHWC; every kernel streams HBM with the channel index on the fastest lanes.
-#include "common.h"
+#include "reduce_common.h"
 
 #include <cstdlib>
 
 namespace hyres {
 
-#define GRID_STRIDE(i, n) \
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
-
-static inline int grid_for_r(long long n) {
-    long long b = (n + 255) / 256;
-    return (int)std::max<long long>(1, std::min<long long>(b, 8192));
-}
-// the PW_UNR-unrolled pointwise kernels: each thread takes PW_UNR float4 per pass, 8 blocks of 256 per CU resident
-static inline int pw_grid(long long n4) {
-    long long b = (n4 + 256LL * 4 - 1) / (256LL * 4);
-    return (int)std::max<long long>(1, std::min<long long>(b, 2048));
-}
-
-constexpr int PW_UNR = 4;  // float4 per thread in flight in the pointwise kernels below
 constexpr int SE_PRELU_PARTS = 2048;  // hyres_se_bwd_prelu's slope partials (<= pw_grid's 2048 blocks)
 
 // torch area_pixel_compute_source_index (linear, align_corners=False): max(scale*(o+0.5)-0.5, 0)
@@ -107,31 +93,11 @@ __device__ __forceinline__ void bw_range(float inv, int t, int in, int out, int&
 
 // one block row per input row (blockIdx.y = b*Hi + h): the vertical output range and weights are
 // block-uniform; threads over (w, channel group)
-// the bilinear PReLU fold's block partials (one per 256-thread block: 16,384 at 128^2 x 16) summed in a fixed order and
-// ADDED to the slope gradient, 8 loads in flight per thread
-__global__ __launch_bounds__(256) void slope_sum8_kernel(const float* part, int n, float* dst) {
-    __shared__ float red[256];
-    float s8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int i = threadIdx.x;
-    for (; i + 7 * 256 < n; i += 8 * 256)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s8[k] += part[i + k * 256];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-        if (i + k * 256 < n) s8[k] += part[i + k * 256];
-    red[threadIdx.x] = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) dst[0] += red[0];
-}
-
 // PM (round 6, VEC == 4, acc == 0): the PReLU backward of the layer that produced the up-sampled map folded in —
 // MultiScaleRefine's scales 2 and 3 end in conv + PReLU before the up-sample (enhancement.py:89-95,98-103): gx =
-// pre > 0 ? g : slope * g with g the (G: fp16-rounded) gather sum, as prelu_bwd4_kernel on the stored gradient, and this
-// block's share of sum_{pre <= 0} pre * g in part[block] (PM = 1: pre fp32, 2: pre fp16)
+// pre > 0 ? g : slope * g with g the (G: fp16-rounded) gather sum (prelu_bwd_elem, as prelu_bwd4_kernel on the stored gradient),
+// and this block's share of sum_{pre <= 0} pre * g in part[block] (PM = 1: pre fp32, 2: pre fp16): one per 256-thread
+// block (16,384 at 128^2 x 16), finished by sum_partials8
 template <int VEC, bool G = false, int PM = 0>  // G: gy / gx fp16 (AMP fp16 gradients), fp32 sums
 __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* gy, int ldgy, float* gx, int ldgx, int B,
                                                            int Hi, int Wi, int Ho, int Wo, int C, float sh, float sw,
@@ -182,10 +148,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* gy, int 
             const float pv[4] = {pv4.x, pv4.y, pv4.z, pv4.w};
             float o[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!(pv[k] > 0.f)) pslope += pv[k] * o[k];
-                o[k] = pv[k] > 0.f ? o[k] : a * o[k];
-            }
+            for (int k = 0; k < 4; ++k) o[k] = prelu_bwd_elem(pv[k], o[k], a, pslope);
             stv4<G>(gx, gp, make_float4(o[0], o[1], o[2], o[3]));
         } else if constexpr (VEC == 4) {
             if (acc) {
@@ -282,9 +245,8 @@ __global__ void se_fc_kernel(const float* part, int nch, const float* w1, const 
         sgate[b * C + c] = 1.0f / (1.0f + expf(-s));
     }
 }
-// fp16 activations (autocast inference): x, y fp16, 4 channels per thread
-// y = x * gate[b][c], 4 channels per thread (C % 4 == 0), 32-bit indices (B * HW * C / 4 < 2^31, host), UNR in flight;
-// H: x, y fp16 (autocast inference)
+// y = x * gate[b][c], 4 channels per thread (C % 4 == 0), 32-bit indices (B * HW * C / 4 < 2^31, host), PW_UNR float4
+// loads in flight per thread; H: x, y fp16 (autocast inference)
 template <bool H>
 __global__ __launch_bounds__(256) void se_scale4_kernel(const float* x, const float* sgate, float* y, int B, int HW,
                                                         int C) {
@@ -403,44 +365,19 @@ __global__ void se_fc_bwd_kernel(const float* part, int nch, int B, const float*
         gpool[idx] = s / (float)HW;
     }
 }
-// gx = gy * gate[b][c] + gpool[b][c], 4 channels per thread (as se_scale4_kernel)
-template <bool G>
+// gx = gy * gate[b][c] + gpool[b][c] (as se_scale4_kernel); G: gy / gx fp16.
+// PRELU: the producing PReLU's backward folded in (hyres_se_bwd_prelu): gx = PReLU'(pre) * (gy * gate + gpool) and this
+// block's share of the slope gradient sum_{pre <= 0} pre * (gy * gate + gpool) in part[blockIdx.x] (finished by
+// prelu_slope_sum), elements in prelu_bwd4_kernel's order (prelu_bwd_elem). Round 6, AMP: H = pre fp16 (fp16
+// activations); with G the gradient is rounded to fp16 first, the unfused chain's stored value
+template <bool G, bool PRELU = false, bool H = false>
 __global__ __launch_bounds__(256) void se_bwd_x4_kernel(const float* gy, const float* sgate, const float* gpool,
-                                                        float* gx, int B, int HW, int C) {
+                                                        float* gx, int B, int HW, int C, const float* pre,
+                                                        const float* slope, float* part) {
     const int C4 = C >> 2, HWC4 = HW * C4;
     const int n = B * HWC4;
     const int stride = gridDim.x * 256;
-    for (int i0 = blockIdx.x * 256 + threadIdx.x; i0 < n; i0 += stride * PW_UNR) {
-        float4 v[PW_UNR];
-#pragma unroll
-        for (int u = 0; u < PW_UNR; ++u) {
-            const int i = i0 + u * stride;
-            if (i < n) v[u] = ldv4<G>(gy, 4LL * i);
-        }
-#pragma unroll
-        for (int u = 0; u < PW_UNR; ++u) {
-            const int i = i0 + u * stride;
-            if (i >= n) continue;
-            const int b = i / HWC4;
-            const int c = 4 * (i - (i / C4) * C4);
-            const float4 gt = ld4(sgate + b * C + c), gp = ld4(gpool + b * C + c);
-            stv4<G>(gx, 4LL * i, make_float4(v[u].x * gt.x + gp.x, v[u].y * gt.y + gp.y, v[u].z * gt.z + gp.z,
-                                             v[u].w * gt.w + gp.w));
-        }
-    }
-}
-// the same with the producing PReLU's backward folded in (hyres_se_bwd_prelu, fp32): gx = PReLU'(pre) * (gy * gate + gpool)
-// and this block's share of the slope gradient sum_{pre <= 0} pre * (gy * gate + gpool) in part[blockIdx.x], elements
-// in the same order as prelu_bwd4_kernel's per-thread sums. Round 6, AMP: H = pre fp16 (fp16 activations), G = gy / gx
-// fp16 (fp16 gradients: the gradient is rounded to fp16 first, the unfused chain's stored value)
-template <bool H = false, bool G = false>
-__global__ __launch_bounds__(256) void se_bwd_x4_prelu_kernel(const float* gy, const float* sgate, const float* gpool,
-                                                              float* gx, int B, int HW, int C, const float* pre,
-                                                              const float* slope, float* part) {
-    const int C4 = C >> 2, HWC4 = HW * C4;
-    const int n = B * HWC4;
-    const int stride = gridDim.x * 256;
-    const float a = slope[0];
+    const float a = PRELU ? slope[0] : 0.f;
     float ps = 0.f;
     for (int i0 = blockIdx.x * 256 + threadIdx.x; i0 < n; i0 += stride * PW_UNR) {
         float4 v[PW_UNR], pv[PW_UNR];
@@ -449,7 +386,7 @@ __global__ __launch_bounds__(256) void se_bwd_x4_prelu_kernel(const float* gy, c
             const int i = i0 + u * stride;
             if (i < n) {
                 v[u] = ldv4<G>(gy, 4LL * i);
-                pv[u] = ldv4<H>(pre, 4LL * i);
+                if constexpr (PRELU) pv[u] = ldv4<H>(pre, 4LL * i);
             }
         }
 #pragma unroll
@@ -460,36 +397,22 @@ __global__ __launch_bounds__(256) void se_bwd_x4_prelu_kernel(const float* gy, c
             const int c = 4 * (i - (i / C4) * C4);
             const float4 gt = ld4(sgate + b * C + c), gp = ld4(gpool + b * C + c);
             float o[4] = {v[u].x * gt.x + gp.x, v[u].y * gt.y + gp.y, v[u].z * gt.z + gp.z, v[u].w * gt.w + gp.w};
-            const float q[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w};
+            if constexpr (PRELU) {
+                const float q[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if constexpr (G) o[k] = (float)(_Float16)o[k];
-                if (!(q[k] > 0.f)) ps += q[k] * o[k];
-                o[k] = q[k] > 0.f ? o[k] : a * o[k];
+                for (int k = 0; k < 4; ++k) {
+                    if constexpr (G) o[k] = (float)(_Float16)o[k];
+                    o[k] = prelu_bwd_elem(q[k], o[k], a, ps);
+                }
             }
             stv4<G>(gx, 4LL * i, make_float4(o[0], o[1], o[2], o[3]));
         }
     }
-    __shared__ float red[256];
-    red[threadIdx.x] = ps;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
+    if constexpr (PRELU) {
+        __shared__ float red[256];
+        const float r = block_sum256(ps, red);
+        if (threadIdx.x == 0) part[blockIdx.x] = r;
     }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void se_prelu_slope_sum_kernel(const float* part, int n, float* dst) {
-    __shared__ float red[256];
-    float v = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) dst[0] += red[0];
 }
 template <bool G = false>
 __global__ void se_bwd_x_kernel(const float* gy, const float* sgate, const float* gpool, float* gx, int B, int HW,
@@ -503,10 +426,16 @@ __global__ void se_bwd_x_kernel(const float* gy, const float* sgate, const float
 }
 
 // ---------------------------------------------------------------- SpatialAttention
-// One wave per pixel (C <= 256, C % 4 == 0: float4 per lane): channel mean, max and the first-occurrence
-// argmax (torch.max(dim=1) on CPU keeps the first maximal index; the backward routes g_max there).
-// channel mean / max (+ first argmax, torch.max semantics) per pixel: 16 lanes per pixel (4 pixels per wave,
-// each lane a float4 stride over the channels), folded with 4 xor-shuffles
+// running max and its first index over the float4 at channels [c, c + 4)
+__device__ __forceinline__ void amax4(const float4& v, int c, float& m, int& mi) {
+    if (v.x > m) { m = v.x; mi = c; }
+    if (v.y > m) { m = v.y; mi = c + 1; }
+    if (v.z > m) { m = v.z; mi = c + 2; }
+    if (v.w > m) { m = v.w; mi = c + 3; }
+}
+// channel mean, max and the first-occurrence argmax per pixel (torch.max(dim=1) on CPU keeps the first maximal index;
+// the backward routes g_max there): 16 lanes per pixel (4 pixels per wave, each lane a float4 stride over the C % 4 == 0
+// channels), folded with 4 xor-shuffles
 // NC > 0 (round 6: C = 64 * NC, MultiScaleRefine's 192): the lane's NC float4 loads are all issued before the first
 // compare — the runtime-bounded loop waited on each in turn (191 us at 256^2 x 16 x 192 fp32, ~4.2 TB/s); the same
 // order of sums and compares, bit-identical
@@ -525,23 +454,16 @@ __global__ __launch_bounds__(256) void sa_pool_kernel(const float* x, float* poo
             for (int k = 0; k < NC; ++k) vv[k] = ldv4<H>(x, xp + 4 * l16 + 64 * k);
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
-                const int c = 4 * l16 + 64 * k;
                 const float4 v = vv[k];
                 s += (v.x + v.y) + (v.z + v.w);
-                if (v.x > m) { m = v.x; mi = c; }
-                if (v.y > m) { m = v.y; mi = c + 1; }
-                if (v.z > m) { m = v.z; mi = c + 2; }
-                if (v.w > m) { m = v.w; mi = c + 3; }
+                amax4(v, 4 * l16 + 64 * k, m, mi);
             }
         }
     } else if (ok) {
         for (int c = 4 * l16; c < C; c += 64) {
             const float4 v = ldv4<H>(x, xp + c);
             s += (v.x + v.y) + (v.z + v.w);
-            if (v.x > m) { m = v.x; mi = c; }
-            if (v.y > m) { m = v.y; mi = c + 1; }
-            if (v.z > m) { m = v.z; mi = c + 2; }
-            if (v.w > m) { m = v.w; mi = c + 3; }
+            amax4(v, c, m, mi);
         }
     }
     for (int off = 8; off > 0; off >>= 1) {
@@ -603,6 +525,25 @@ __device__ __forceinline__ void sa_tile_of(int B, int H, int W, int& b, int& h0,
     h0 = ty * SA_T;
     w0 = tx * SA_T;
 }
+// the 7x7 taps and the tile's pooled2 planes with their 3-pixel halo (zero outside the image) into LDS; GL: glogit too
+template <bool GL>
+__device__ __forceinline__ void sa_stage_tile(const float* w, const float* pooled2, const float* glogit, int b, int h0,
+                                              int w0, int H, int W, float* ws, float (*pl)[SA_L][SA_L + 1],
+                                              float (*gl)[SA_L + 1]) {
+    const int tid = threadIdx.x;
+    if (tid < 98) ws[tid] = w[tid];
+    for (int e = tid; e < SA_L * SA_L; e += 256) {
+        const int ly = e / SA_L, lx = e - ly * SA_L;
+        const int ih = h0 - 3 + ly, iw = w0 - 3 + lx;
+        const bool ok = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
+        const long long p = ((long long)b * H + ih) * W + iw;
+        const float2 v = ok ? *reinterpret_cast<const float2*>(pooled2 + p * 2) : make_float2(0.f, 0.f);
+        if constexpr (GL) gl[ly][lx] = ok ? glogit[p] : 0.f;
+        pl[0][ly][lx] = v.x;
+        pl[1][ly][lx] = v.y;
+    }
+    __syncthreads();
+}
 // forward: attn = sigmoid(sum_{ch, kh, kw} w * pooled2), the per-pixel kernel's summation order (bit-identical)
 __global__ __launch_bounds__(256) void sa_conv_tiled_kernel(const float* pooled2, const float* w, float* attn, int B,
                                                             int H, int W) {
@@ -611,17 +552,7 @@ __global__ __launch_bounds__(256) void sa_conv_tiled_kernel(const float* pooled2
     int b, h0, w0;
     sa_tile_of(B, H, W, b, h0, w0);
     const int tid = threadIdx.x;
-    if (tid < 98) ws[tid] = w[tid];
-    for (int e = tid; e < SA_L * SA_L; e += 256) {
-        const int ly = e / SA_L, lx = e - ly * SA_L;
-        const int ih = h0 - 3 + ly, iw = w0 - 3 + lx;
-        const bool ok = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-        const float2 v = ok ? *reinterpret_cast<const float2*>(pooled2 + (((long long)b * H + ih) * W + iw) * 2)
-                            : make_float2(0.f, 0.f);
-        pl[0][ly][lx] = v.x;
-        pl[1][ly][lx] = v.y;
-    }
-    __syncthreads();
+    sa_stage_tile<false>(w, pooled2, nullptr, b, h0, w0, H, W, ws, pl, nullptr);
     const int ty = tid / SA_T, tx = tid % SA_T;
     const int hh = h0 + ty, ww = w0 + tx;
     if (hh >= H || ww >= W) return;
@@ -641,7 +572,7 @@ __global__ __launch_bounds__(256) void sa_conv_tiled_kernel(const float* pooled2
     attn[((long long)b * H + hh) * W + ww] = 1.0f / (1.0f + expf(-s));
 }
 // backward: gpooled2 (the per-pixel kernel's order: bit-identical) and per-tile weight-gradient partials (98 taps x 2
-// half-tiles of 8 rows, summed in a fixed order); C > 0: the mean's gradient stored divided by C (HYRES_EPI_SA_BWD)
+// half-tiles of 8 rows, summed in a fixed order, finished by sum_partials_cols); C > 0: the mean's gradient stored divided by C (HYRES_EPI_SA_BWD)
 __global__ __launch_bounds__(256) void sa_bwd_conv_tiled_kernel(const float* glogit, const float* pooled2,
                                                                 const float* w, float* gpooled2, float* wpart, int B,
                                                                 int H, int W, int C) {
@@ -652,18 +583,7 @@ __global__ __launch_bounds__(256) void sa_bwd_conv_tiled_kernel(const float* glo
     int b, h0, w0;
     sa_tile_of(B, H, W, b, h0, w0);
     const int tid = threadIdx.x;
-    if (tid < 98) ws[tid] = w[tid];
-    for (int e = tid; e < SA_L * SA_L; e += 256) {
-        const int ly = e / SA_L, lx = e - ly * SA_L;
-        const int ih = h0 - 3 + ly, iw = w0 - 3 + lx;
-        const bool ok = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-        const long long p = ((long long)b * H + ih) * W + iw;
-        const float2 v = ok ? *reinterpret_cast<const float2*>(pooled2 + p * 2) : make_float2(0.f, 0.f);
-        gl[ly][lx] = ok ? glogit[p] : 0.f;
-        pl[0][ly][lx] = v.x;
-        pl[1][ly][lx] = v.y;
-    }
-    __syncthreads();
+    sa_stage_tile<true>(w, pooled2, glogit, b, h0, w0, H, W, ws, pl, gl);
     {
         const int ty = tid / SA_T, tx = tid % SA_T;
         const int hh = h0 + ty, ww = w0 + tx;
@@ -696,20 +616,6 @@ __global__ __launch_bounds__(256) void sa_bwd_conv_tiled_kernel(const float* glo
     __syncthreads();
     if (tid < 98) wpart[(long long)blockIdx.x * 98 + tid] = acc + half2s[tid];
 }
-// one block per weight tap: 256 threads fold the per-block partials (deterministic order)
-__global__ void sa_bwd_wfinal_kernel(const float* wpart, int nb, float* gw) {
-    __shared__ float red[256];
-    const int k = blockIdx.x;
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nb; b += 256) s += wpart[(long long)b * 98 + k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) gw[k] += red[0];
-}
 // bwd 3: gx = gy*a + g_avg/C + [c == argmax] * g_max     (float4 over channels; argmax saved by the pool)
 template <bool G = false>
 __global__ void sa_bwd_x_kernel(const float* gy, const float* attn, const float* gpooled2, const int* amax, float* gx,
@@ -732,12 +638,26 @@ __global__ void sa_bwd_x_kernel(const float* gy, const float* attn, const float*
     }
 }
 
+// the two sa_fold_bwd kernels' block partials, part[block][C + 1]: d bias per channel (the NG pixel groups' sums in
+// rb[g][c], folded in group order) and d slope (the threads' ss: block_sum256); finished by sum_partials_cols
+template <int NG>
+__device__ __forceinline__ void sa_fold_store_partials(const float (*rb)[68], float ss, float* rs, float* part, int C) {
+    const float r = block_sum256(ss, rs);  // its first barrier also orders the callers' writes of rb
+    if (threadIdx.x < C) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) t += rb[g][threadIdx.x];
+        part[(long long)blockIdx.x * (C + 1) + threadIdx.x] = t;
+    }
+    if (threadIdx.x == 0) part[(long long)blockIdx.x * (C + 1) + C] = r;
+}
 // ---- training with SpatialAttention's multiply folded into the fusion 1x1 (HYRES_EPI_ROWSCALE forward):
 // h = PReLU(pre), pre = attn[p] * (W multi)[p] + b. Per pixel (16 lanes, a float4 of the C <= 64 channels each):
 // gp = PReLU-backward(gy); gs = attn * gp (the fusion 1x1's weight- and input-gradient operand: d W = sum gs x multi,
 // d multi = W^T gs, exactly the reference's gradients through multi * attn); glogit = (1 - attn) * sum_o gp (pre - b),
 // which is attn (1 - attn) * sum_o gp z with attn z = pre - b (the gradient at the attention logit, no division by
-// attn). Per-block partials of d bias (sum gp) and d slope (sum over pre <= 0 of gy pre, prelu_bwd4_kernel's order).
+// attn). Per-block partials of d bias (sum gp) and d slope (sum over pre <= 0 of gy pre: prelu_bwd_elem in
+// prelu_bwd4_kernel's order).
 __global__ __launch_bounds__(256) void sa_fold_bwd_kernel(const float* pre, int ldpre, const float* gy, int ldg,
                                                           const float* attn, const float* bias, const float* slope,
                                                           float* gs, float* glogit, float* part, long long P, int C) {
@@ -756,12 +676,11 @@ __global__ __launch_bounds__(256) void sa_fold_bwd_kernel(const float* pre, int 
         const float4 pv = cok ? *reinterpret_cast<const float4*>(pre + p * ldpre + c) : z4;
         const float4 gv = cok ? *reinterpret_cast<const float4*>(gy + p * ldg + c) : z4;
         const float at = attn[p];
-        const float4 gp = make_float4(pv.x > 0.f ? gv.x : a * gv.x, pv.y > 0.f ? gv.y : a * gv.y,
-                                      pv.z > 0.f ? gv.z : a * gv.z, pv.w > 0.f ? gv.w : a * gv.w);
-        if (!(pv.x > 0.f)) ss += pv.x * gv.x;
-        if (!(pv.y > 0.f)) ss += pv.y * gv.y;
-        if (!(pv.z > 0.f)) ss += pv.z * gv.z;
-        if (!(pv.w > 0.f)) ss += pv.w * gv.w;
+        float4 gp;
+        gp.x = prelu_bwd_elem(pv.x, gv.x, a, ss);
+        gp.y = prelu_bwd_elem(pv.y, gv.y, a, ss);
+        gp.z = prelu_bwd_elem(pv.z, gv.z, a, ss);
+        gp.w = prelu_bwd_elem(pv.w, gv.w, a, ss);
         bs.x += gp.x; bs.y += gp.y; bs.z += gp.z; bs.w += gp.w;
         float d = (gp.x * (pv.x - b.x) + gp.y * (pv.y - b.y)) + (gp.z * (pv.z - b.z) + gp.w * (pv.w - b.w));
         if (cok) *reinterpret_cast<float4*>(gs + p * C + c) = make_float4(at * gp.x, at * gp.y, at * gp.z, at * gp.w);
@@ -769,19 +688,7 @@ __global__ __launch_bounds__(256) void sa_fold_bwd_kernel(const float* pre, int 
         if (l16 == 0) glogit[p] = d * (1.0f - at);
     }
     if (cok) *reinterpret_cast<float4*>(&rb[grp][c]) = bs;
-    rs[threadIdx.x] = ss;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) rs[threadIdx.x] += rs[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x < C) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) t += rb[g][threadIdx.x];
-        part[(long long)blockIdx.x * (C + 1) + threadIdx.x] = t;
-    }
-    if (threadIdx.x == 0) part[(long long)blockIdx.x * (C + 1) + C] = rs[0];
+    sa_fold_store_partials<16>(rb, ss, rs, part, C);
 }
 // The fp16-activation build (AMP training): 8 lanes per pixel, 8 channels (one 16-byte fp16 row piece) each — the
 // 16-lane float4 mapping above moves fp16 rows as 8-byte pieces and measured 169 us at 256^2 x 16 (r7h). Same
@@ -831,8 +738,7 @@ __global__ __launch_bounds__(256) void sa_fold_bwd_h8_kernel(const float* pre, i
         float gp[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            gp[k] = pv[k] > 0.f ? gv[k] : a * gv[k];
-            if (!(pv[k] > 0.f)) ss += pv[k] * gv[k];
+            gp[k] = prelu_bwd_elem(pv[k], gv[k], a, ss);
             bs[k] += gp[k];
         }
         // sa_fold_bwd_kernel's pairing within each float4, then the two halves
@@ -856,37 +762,7 @@ __global__ __launch_bounds__(256) void sa_fold_bwd_h8_kernel(const float* pre, i
 #pragma unroll
         for (int k = 0; k < 8; ++k) rb[grp][c + k] = bs[k];
     }
-    rs[threadIdx.x] = ss;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) rs[threadIdx.x] += rs[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x < C) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 32; ++g) t += rb[g][threadIdx.x];
-        part[(long long)blockIdx.x * (C + 1) + threadIdx.x] = t;
-    }
-    if (threadIdx.x == 0) part[(long long)blockIdx.x * (C + 1) + C] = rs[0];
-}
-// one block per output (C bias channels, then the slope): the partials folded in a fixed order, ADDED to the gradient
-__global__ __launch_bounds__(256) void sa_fold_final_kernel(const float* part, int nb, int C, float* dbias,
-                                                            float* dslope) {
-    __shared__ float red[256];
-    const int k = blockIdx.x;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nb; i += 256) s += part[(long long)i * (C + 1) + k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (k < C) dbias[k] += red[0];
-        else dslope[0] += red[0];
-    }
+    sa_fold_store_partials<32>(rb, ss, rs, part, C);
 }
 
 }  // namespace hyres
@@ -922,28 +798,26 @@ template <bool G>
 static int bilinear_bwd_impl(const float* gy, int ldgy, float* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
                              float scale_h, float scale_w, int accumulate, hyres_stream_t s) {
     HY_REQUIRE(gy && gx, HYRES_E_ARG, "bilinear_bwd: NULL");
-    const unsigned am = G ? 7u : 15u;  // 4-element vectors: 8 B (fp16) / 16 B (fp32)
-    const bool vec = C % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && (reinterpret_cast<uintptr_t>(gy) & am) == 0 &&
-                     (reinterpret_cast<uintptr_t>(gx) & am) == 0;
+    const bool vec = C % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && aligned_v4(gy, G) && aligned_v4(gx, G);
     HY_REQUIRE((long long)B * Hi <= 65535 && (long long)Wi * C < (1LL << 30), HYRES_E_SHAPE, "bilinear_bwd: too large");
     const dim3 grid(ceil_div((long long)Wi * (vec ? C / 4 : C), 256), B * Hi);
-    for (int S = 2; S <= 4 && vec; S += 2) {
-        if (scale_h != (float)S || scale_w != (float)S || Hi != S * Ho || Wi != S * Wo) continue;
-        if (S == 2)
-            hipLaunchKernelGGL((bilinear_down_bwd_kernel<2, G>), grid, dim3(256), 0, as_stream(s), gy, ldgy, gx, ldgx,
-                               Hi, Wi, Ho, Wo, C, accumulate);
-        else
-            hipLaunchKernelGGL((bilinear_down_bwd_kernel<4, G>), grid, dim3(256), 0, as_stream(s), gy, ldgy, gx, ldgx,
-                               Hi, Wi, Ho, Wo, C, accumulate);
-        return HY_LAUNCH_CHECK("bilinear_down_bwd");
-    }
-    if (vec)
+    const auto down = [&](int S) {  // an exact integer down-sampling by S
+        return vec && scale_h == (float)S && scale_w == (float)S && Hi == S * Ho && Wi == S * Wo;
+    };
+    const int S = down(2) ? 2 : down(4) ? 4 : 0;
+    if (S == 2)
+        hipLaunchKernelGGL((bilinear_down_bwd_kernel<2, G>), grid, dim3(256), 0, as_stream(s), gy, ldgy, gx, ldgx, Hi, Wi,
+                           Ho, Wo, C, accumulate);
+    else if (S == 4)
+        hipLaunchKernelGGL((bilinear_down_bwd_kernel<4, G>), grid, dim3(256), 0, as_stream(s), gy, ldgy, gx, ldgx, Hi, Wi,
+                           Ho, Wo, C, accumulate);
+    else if (vec)
         hipLaunchKernelGGL((bilinear_bwd_kernel<4, G>), grid, dim3(256), 0, as_stream(s), gy, ldgy, gx, ldgx, B, Hi, Wi,
                            Ho, Wo, C, scale_h, scale_w, accumulate, nullptr, 0, nullptr, nullptr);
     else
         hipLaunchKernelGGL((bilinear_bwd_kernel<1, G>), grid, dim3(256), 0, as_stream(s), gy, ldgy, gx, ldgx, B, Hi, Wi,
                            Ho, Wo, C, scale_h, scale_w, accumulate, nullptr, 0, nullptr, nullptr);
-    return HY_LAUNCH_CHECK("bilinear_bwd");
+    return HY_LAUNCH_CHECK(S ? "bilinear_down_bwd" : "bilinear_bwd");
 }
 static dim3 bilinear_bwd_grid(int B, int Hi, int Wi, int C) { return dim3(ceil_div((long long)Wi * (C / 4), 256), B * Hi); }
 }  // extern "C++"
@@ -966,27 +840,15 @@ int hyres_bilinear_bwd_prelu(const void* gy, int ldgy, void* gx, int ldgx, int B
                "bilinear_bwd_prelu: workspace");
     const dim3 grid = bilinear_bwd_grid(B, Hi, Wi, C);
     hipStream_t st = as_stream(s);
-    const float* g = (const float*)gy;
-    float* x = (float*)gx;
-    const float* p = (const float*)pre;
     float* part = (float*)ws;
-#define HY_BBP(GG, PMV)                                                                                                  \
-    hipLaunchKernelGGL((bilinear_bwd_kernel<4, GG, PMV>), grid, dim3(256), 0, st, g, ldgy, x, ldgx, B, Hi, Wi, Ho, Wo, C, \
-                       scale_h, scale_w, 0, p, ldpre, slope, part)
-    if (G && H) {
-        HY_BBP(true, 2);
-    } else if (G) {
-        HY_BBP(true, 1);
-    } else if (H) {
-        HY_BBP(false, 2);
-    } else {
-        HY_BBP(false, 1);
-    }
-#undef HY_BBP
-    int rc = HY_LAUNCH_CHECK("bilinear_bwd_prelu");
+    const int rc = dispatch_bool2(G, H, [&](auto GG, auto HH) {
+        hipLaunchKernelGGL((bilinear_bwd_kernel<4, GG, decltype(HH)::value ? 2 : 1>), grid, dim3(256), 0, st,
+                           (const float*)gy, ldgy, (float*)gx, ldgx, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w, 0,
+                           (const float*)pre, ldpre, slope, part);
+        return HY_LAUNCH_CHECK("bilinear_bwd_prelu");
+    });
     if (rc) return rc;
-    hipLaunchKernelGGL(slope_sum8_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)(grid.x * grid.y), dslope);
-    return HY_LAUNCH_CHECK("bilinear_bwd_prelu_final");
+    return sum_partials8(part, (int)(grid.x * grid.y), dslope, 1, st, "bilinear_bwd_prelu_final");
 }
 int hyres_bilinear_bwd(const void* gy, int ldgy, void* gx, int ldgx, int B, int Hi, int Wi, int Ho, int Wo, int C,
                        float scale_h, float scale_w, int accumulate, int f16, hyres_stream_t s) {
@@ -997,6 +859,9 @@ int hyres_bilinear_bwd(const void* gy, int ldgy, void* gx, int ldgx, int B, int 
     return bilinear_bwd_impl<false>((const float*)gy, ldgy, (float*)gx, ldgx, B, Hi, Wi, Ho, Wo, C, scale_h, scale_w,
                                     accumulate, s);
 }
+
+// the float4 pool kernels' channel layout: 256 threads = (C / 4 channel groups) x (pixel lanes)
+static bool se_vec_ok(int C) { return C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0; }
 
 static int se_chunks(int HW) { return std::max(1, std::min(64, (HW + 1023) / 1024)); }
 
@@ -1009,7 +874,7 @@ int hyres_se_fwd(const void* xv, const float* w1, const float* w2, void* yv, flo
     float* y = (float*)yv;
     HY_REQUIRE(x && w1 && w2 && y && pooled && hidden && sgate, HYRES_E_ARG, "se_fwd: NULL");
     // fp16 x / y: the 4-vector kernels only
-    HY_REQUIRE(!f16 || (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && aligned8(x) && aligned8(y)), HYRES_E_ALIGN,
+    HY_REQUIRE(!f16 || (se_vec_ok(C) && aligned8(x) && aligned8(y)), HYRES_E_ALIGN,
                "se_fwd: fp16 needs C %% 4 == 0, 256 %% (C/4) == 0, 8B-aligned x/y");
     const int nch = se_chunks(HW);
     HY_REQUIRE(ws && ws_bytes >= (long long)B * nch * C * 4, HYRES_E_WORKSPACE, "se_fwd: workspace");
@@ -1018,7 +883,7 @@ int hyres_se_fwd(const void* xv, const float* w1, const float* w2, void* yv, flo
     if (f16)
         hipLaunchKernelGGL((se_pool4_kernel<false, true>), dim3(B, nch), dim3(256), 0, st, x, (const float*)nullptr, HW, C,
                            per, (float*)ws);
-    else if (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && aligned16(x))
+    else if (se_vec_ok(C) && aligned16(x))
         hipLaunchKernelGGL(se_pool4_kernel<false>, dim3(B, nch), dim3(256), 0, st, x, (const float*)nullptr, HW, C,
                            per, (float*)ws);
     else
@@ -1038,7 +903,7 @@ int hyres_se_fwd(const void* xv, const float* w1, const float* w2, void* yv, flo
         hipLaunchKernelGGL(se_scale4_kernel<false>, dim3(pw_grid(n / 4)), dim3(256), 0, st, x, (const float*)sgate, y, B,
                            HW, C);
     else
-        hipLaunchKernelGGL(se_scale_kernel, dim3(grid_for_r(n)), dim3(256), 0, st, x, (const float*)sgate, y, B, HW, C);
+        hipLaunchKernelGGL(se_scale_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, (const float*)sgate, y, B, HW, C);
     return HY_LAUNCH_CHECK("se_scale");
 }
 
@@ -1057,7 +922,7 @@ static int se_bwd_impl(const float* x, const float* gy, const float* w1, const f
     float* part = (float*)ws;
     float* gpool = part + (long long)B * nch * C;
     hipStream_t st = as_stream(s);
-    if (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && aligned16(x) && aligned16(gy))
+    if (se_vec_ok(C) && aligned16(x) && aligned16(gy))
         hipLaunchKernelGGL((se_pool4_kernel<true, H, G>), dim3(B, nch), dim3(256), 0, st, x, gy, HW, C, per, part);
     else
         hipLaunchKernelGGL((se_bwd_pool_kernel<H, G>), dim3(B, nch), dim3(256), 0, st, x, gy, HW, C, per, part);
@@ -1068,23 +933,19 @@ static int se_bwd_impl(const float* x, const float* gy, const float* w1, const f
     rc = HY_LAUNCH_CHECK("se_fc_bwd");
     if (rc) return rc;
     long long n = (long long)B * HW * C;
-    const unsigned am = G ? 7u : 15u;
     if (pre) {  // the PReLU-folded form (alignment checked by the entry points)
         float* pp = gpool + (long long)B * C;
         const int nb = std::min(pw_grid(n / 4), SE_PRELU_PARTS);
-        hipLaunchKernelGGL((se_bwd_x4_prelu_kernel<H, G>), dim3(nb), dim3(256), 0, st, gy, sgate, (const float*)gpool, gx,
+        hipLaunchKernelGGL((se_bwd_x4_kernel<G, true, H>), dim3(nb), dim3(256), 0, st, gy, sgate, (const float*)gpool, gx,
                            B, HW, C, pre, slope, pp);
         rc = HY_LAUNCH_CHECK("se_bwd_x4_prelu");
-        if (rc) return rc;
-        hipLaunchKernelGGL(se_prelu_slope_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)pp, nb, dslope);
-        return HY_LAUNCH_CHECK("se_prelu_slope_sum");
+        return rc ? rc : prelu_slope_sum(pp, nb, dslope, st);
     }
-    if (C % 4 == 0 && (reinterpret_cast<uintptr_t>(gy) & am) == 0 && (reinterpret_cast<uintptr_t>(gx) & am) == 0 &&
-        n / 4 < (1LL << 31))
+    if (C % 4 == 0 && aligned_v4(gy, G) && aligned_v4(gx, G) && n / 4 < (1LL << 31))
         hipLaunchKernelGGL(se_bwd_x4_kernel<G>, dim3(pw_grid(n / 4)), dim3(256), 0, st, gy, sgate, (const float*)gpool,
-                           gx, B, HW, C);
+                           gx, B, HW, C, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
     else
-        hipLaunchKernelGGL(se_bwd_x_kernel<G>, dim3(grid_for_r(n)), dim3(256), 0, st, gy, sgate, (const float*)gpool, gx,
+        hipLaunchKernelGGL(se_bwd_x_kernel<G>, dim3(grid_for(n)), dim3(256), 0, st, gy, sgate, (const float*)gpool, gx,
                            B, HW, C);
     return HY_LAUNCH_CHECK("se_bwd_x");
 }
@@ -1148,7 +1009,7 @@ static int spatial_attn_fwd_impl(const float* x, const float* w, float* pooled2,
     rc = HY_LAUNCH_CHECK("sa_conv");
     if (rc) return rc;
     if (!y) return ok();  // the attention map only (the multiply folded into the consumer: HYRES_EPI_ROWSCALE)
-    hipLaunchKernelGGL(sa_mul_kernel<HF>, dim3(grid_for_r(P * C / 4)), dim3(256), 0, st, x, (const float*)attn, y, P, C);
+    hipLaunchKernelGGL(sa_mul_kernel<HF>, dim3(grid_for(P * C / 4)), dim3(256), 0, st, x, (const float*)attn, y, P, C);
     return HY_LAUNCH_CHECK("sa_mul");
 }
 }  // extern "C++"
@@ -1165,9 +1026,7 @@ static int spatial_attn_bwd_impl(const float* x, const float* w, const float* po
                                  const float* attn, const float* gy, float* gx, float* gw, int B, int H, int W, int C,
                                  void* ws, long long ws_bytes, hyres_stream_t s) {
     HY_REQUIRE(x && w && pooled2 && argmax && attn && gy && gx && gw, HYRES_E_ARG, "spatial_attn_bwd: NULL");
-    const unsigned am = G ? 7u : 15u;
-    HY_REQUIRE(C % 4 == 0 && C <= 1024 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(gy) & am) == 0 && (reinterpret_cast<uintptr_t>(gx) & am) == 0,
+    HY_REQUIRE(C % 4 == 0 && C <= 1024 && aligned8(x) && aligned_v4(gy, G) && aligned_v4(gx, G),
                HYRES_E_ALIGN, "spatial_attn: C %% 4 == 0 and aligned x/gy/gx required");
     long long P = (long long)B * H * W;
     HY_REQUIRE(ws && ws_bytes >= hyres_spatial_attn_workspace_bytes(B, H, W), HYRES_E_WORKSPACE,
@@ -1185,10 +1044,9 @@ static int spatial_attn_bwd_impl(const float* x, const float* w, const float* po
                        wpart, B, H, W, 0);
     rc = HY_LAUNCH_CHECK("sa_bwd_conv");
     if (rc) return rc;
-    hipLaunchKernelGGL(sa_bwd_wfinal_kernel, dim3(98), dim3(256), 0, st, (const float*)wpart, nb, gw);
-    rc = HY_LAUNCH_CHECK("sa_bwd_wfinal");
+    rc = sum_partials_cols(wpart, nb, 98, gw, 98, nullptr, 0, st, "sa_bwd_wfinal");
     if (rc) return rc;
-    hipLaunchKernelGGL(sa_bwd_x_kernel<G>, dim3(grid_for_r(P * C / 4)), dim3(256), 0, st, gy, attn, (const float*)gp2,
+    hipLaunchKernelGGL(sa_bwd_x_kernel<G>, dim3(grid_for(P * C / 4)), dim3(256), 0, st, gy, attn, (const float*)gp2,
                        argmax, gx, P, C);
     return HY_LAUNCH_CHECK("sa_bwd_x");
 }
@@ -1224,8 +1082,7 @@ int hyres_sa_fold_bwd(const void* prev, int ldpre, const void* gyv, int ldg, con
                            glogit, (float*)ws, P, C);
     int rc = HY_LAUNCH_CHECK("sa_fold_bwd");
     if (rc) return rc;
-    hipLaunchKernelGGL(sa_fold_final_kernel, dim3(C + 1), dim3(256), 0, st, (const float*)ws, nb, C, dbias, dslope);
-    return HY_LAUNCH_CHECK("sa_fold_final");
+    return sum_partials_cols((const float*)ws, nb, C + 1, dbias, C, dslope, 1, st, "sa_fold_final");  // bias, then slope
 }
 
 int hyres_spatial_attn_bwd_map(const float* glogit, const float* pooled2, const float* w, float* gpooled2, float* gw,
@@ -1241,9 +1098,7 @@ int hyres_spatial_attn_bwd_map(const float* glogit, const float* pooled2, const 
     hipLaunchKernelGGL(sa_bwd_conv_tiled_kernel, dim3(nb), dim3(256), 0, st, glogit, pooled2, w, gpooled2, wpart, B, H,
                        W, C);
     int rc = HY_LAUNCH_CHECK("sa_bwd_conv");
-    if (rc) return rc;
-    hipLaunchKernelGGL(sa_bwd_wfinal_kernel, dim3(98), dim3(256), 0, st, (const float*)wpart, nb, gw);
-    return HY_LAUNCH_CHECK("sa_bwd_wfinal");
+    return rc ? rc : sum_partials_cols(wpart, nb, 98, gw, 98, nullptr, 0, st, "sa_bwd_wfinal");
 }
 
 int hyres_spatial_attn_bwd(const void* x, const float* w, const float* pooled2, const int* argmax, const float* attn,

@@ -116,7 +116,7 @@ def lds_read_hazards(instrs: list[str]) -> list[tuple[str, str]]:
 
 
 def kernels(so_path: str, arch: str = "gfx950") -> list[dict]:
-    """One dict per kernel: name, vgpr, agpr, accum_offset-free allocation, lds, threads, sgpr, scratch."""
+    """One dict per kernel: name, vgpr, agpr, accum_offset-free allocation, lds, threads, sgpr, scratch, tu."""
     docs = []
     with tempfile.TemporaryDirectory() as td:
         for co in _code_objects(so_path, td, arch):
@@ -125,7 +125,7 @@ def kernels(so_path: str, arch: str = "gfx950") -> list[dict]:
             m = re.search(r"^\s*---\n(.*?)^\s*\.\.\.\s*$", notes, re.S | re.M)
             docs.append(yaml.safe_load(m.group(1)))
     out = []
-    for k in (k for d in docs for k in d["amdhsa.kernels"]):
+    for tu, k in ((i, k) for i, d in enumerate(docs) for k in d["amdhsa.kernels"]):
         vg, ag = int(k[".vgpr_count"]), int(k.get(".agpr_count", 0))
         # gfx90a+: .vgpr_count is already the unified total (the arch VGPRs aligned to 4, then the AGPRs at
         # accum_offset; LLVM's NumVGPRsForWavesPerEU) — 395 on a kernel cannot be arch registers alone (v0..v255).
@@ -134,7 +134,8 @@ def kernels(so_path: str, arch: str = "gfx950") -> list[dict]:
         alloc = max(GRANULE, -(-total // GRANULE) * GRANULE)
         out.append({"name": k[".name"], "vgpr": vg, "agpr": ag, "alloc": alloc,
                     "lds": int(k[".group_segment_fixed_size"]), "threads": int(k[".max_flat_workgroup_size"]),
-                    "sgpr": int(k[".sgpr_count"]), "scratch": int(k[".private_segment_fixed_size"])})
+                    "sgpr": int(k[".sgpr_count"]), "scratch": int(k[".private_segment_fixed_size"]),
+                    "tu": tu})  # index of the translation unit's code object in the library
     return out
 
 

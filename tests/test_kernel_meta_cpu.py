@@ -169,3 +169,21 @@ def test_gemm_kernels_instantiations_and_lds(meta):
     got = {n.replace("hyres::", "").replace("void ", "").split("(")[0]: k["lds"] for k, n in zip(ks, names)}
     assert len(got) == len(ks)
     assert got == want, {n: (want.get(n), got.get(n)) for n in set(want) | set(got) if want.get(n) != got.get(n)}
+
+
+def test_refine_kernels_instantiations_and_lds(meta):
+    """The pointwise / refine / VGG kernels (csrc/refine.hip, pointwise.hip, vgg.hip, device code shared in
+    csrc/reduce_common.h) and entropy.hip's eb_bwd_kernel: the set of instantiations and each one's LDS bytes are those
+    of the build before the reductions and PReLU folds were shared (tests/golden/refine_kernels.json, written from that
+    build), less the removed copies: the merged finishing kernels and se_bwd_x4_kernel<G, PRELU, H> stand under their
+    new names with the LDS of the kernels they replace."""
+    with open(os.path.join(HERE, "golden", "refine_kernels.json")) as f:
+        want = json.load(f)
+    ks = list(meta.values())
+    names = kernel_meta.demangle([k["name"] for k in ks])
+    short = [n.replace("hyres::", "").replace("void ", "").split("(")[0] for n in names]
+    tus = {k["tu"] for k, n in zip(ks, short)
+           if n.split("<")[0] in ("bilinear_fwd_kernel", "axpby_kernel", "maxpool2_fwd_kernel")}
+    assert len(tus) == 3, tus  # refine.hip, pointwise.hip, vgg.hip
+    got = {n: k["lds"] for k, n in zip(ks, short) if k["tu"] in tus or n == "eb_bwd_kernel"}
+    assert got == want, {n: (want.get(n), got.get(n)) for n in set(want) | set(got) if want.get(n) != got.get(n)}

@@ -279,7 +279,8 @@ def test_bilinear_bwd_prelu(s, dt):
 
 
 def test_bilinear_bwd_prelu_2100_partials_slope_sum8_tail():
-    """B * Hi = 2100 one-block rows: slope_sum8_kernel folds one full pass of 2048 partials plus a ragged tail of 52."""
+    """B * Hi = 2100 one-block rows: sum_partials_kernel (the eight-in-flight order, reached through sum_partials8)
+    folds one full pass of 2048 partials plus a ragged tail of 52."""
     _bilinear_bwd_prelu(3, 700, 4, 1400, 8, 4, 0.5, 0.5, 0)
 
 
@@ -334,8 +335,9 @@ def _se_grads(k, gy):
     return gx, g1, g2
 
 
-def _run_se(c, dt=0, prelu=False):
-    """hyres_se_fwd, then hyres_se_bwd (or hyres_se_bwd_prelu) on the forward's saved pooled / hidden / gate."""
+def _run_se(c, dt=0, prelu=False, slope_bar=None):
+    """hyres_se_fwd, then hyres_se_bwd (or hyres_se_bwd_prelu) on the forward's saved pooled / hidden / gate.
+    ``slope_bar``: the bar on d slope when it is not the dtype's usual one."""
     L = _L()
     B, HW, C, Cr, off = c
     half, g16 = bool(dt & DT_ACT16), bool(dt & DT_GRAD16)
@@ -387,7 +389,7 @@ def _run_se(c, dt=0, prelu=False):
     if prelu:
         gi, dsl = RR.prelu_bwd_ref(k["pre"], gxr, k["slope"])
         _check("gx", gxv, gi, red)
-        _check("dslope", ds.take().view(()), dsl + 0.625, TOL_AMP if g16 else TOL_SLOPE)
+        _check("dslope", ds.take().view(()), dsl + 0.625, slope_bar or (TOL_AMP if g16 else TOL_SLOPE))
         return
     _check("gx", gxv, gxr, red)
     if not g16:
@@ -417,8 +419,17 @@ def test_se_fwd_bwd_f16(dt):
                               "2x1500x64-act16/se_bwd_x4_prelu<H>", "2x1500x64-act16-grad16/se_bwd_x4_prelu<H,G>"])
 def test_se_bwd_prelu(c, dt):
     """hyres_se_bwd_prelu: the producing PReLU's backward on the input gradient, d slope added to a non-zero start; at
-    2 x 66000 x 64 n / 4 exceeds 2048 x 1024 float4, so every thread makes a second pass."""
+    2 x 66000 x 64 n / 4 exceeds 2048 x 1024 float4, so every thread makes a second pass. The kernel is
+    se_bwd_x4_kernel<G, PRELU = true, H>; its partials are finished by sum_partials_serial_kernel."""
     _run_se(c, dt, prelu=True)
+
+
+@pytest.mark.parametrize("dt", [0, DT_ACT16 | DT_GRAD16], ids=["fp32", "act16-grad16"])
+def test_se_bwd_prelu_258_partials_serial_sum_tail(dt):
+    """1 x (129 x 128) x 64: 264,192 float4 give 258 blocks of slope partials, so sum_partials_serial_kernel (one
+    running sum per thread) makes one full pass of 256 and a ragged second pass of 2. d slope at TOL_SLOPE in both
+    dtypes: the fp16 roundings of 1M gradients (2^-11 each, signs random) average far below it."""
+    _run_se((1, 129 * 128, 64, 4, 0), dt, prelu=True, slope_bar=TOL_SLOPE)
 
 
 def test_se_bwd_refuses_batch_beyond_lds():
@@ -548,7 +559,7 @@ def test_spatial_attn_fwd(bhw, C, fam):
 @pytest.mark.parametrize("bhw,C,fam", SA_PARAMS)
 def test_spatial_attn_bwd(bhw, C, fam):
     """gx routes g_max to the first maximal channel only; gw is added to a non-zero start; 264 tiles run
-    sa_bwd_wfinal_kernel's loop."""
+    sum_partials_cols_kernel's loop (the strided column sum, stride 98) into a second pass."""
     _check_sa_bwd(_sa_case(bhw, C, fam), bhw, C, 0)
 
 
